@@ -9,7 +9,7 @@ test-cpu: build oracle
 test-gpu:
 	python -m pytest tests -x -q -m gpu
 bench:
-	python bench.py
+	python bench.py --full
 profile:
 	bash tools/profile.sh r01
 clean:

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark of the MINCO hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_PER_GPU] [--pieces 8] [--order 4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_PER_GPU] [--pieces 8] [--order 4] [--full]
+                    [--dump-outputs DIR]
 
 `--gpus N` with N > 1 starts its own N ranks (one process per GPU under torch.distributed.run, rendezvous on 127.0.0.1);
 launched BY torch.distributed.run (WORLD_SIZE set) the process is one rank of the job, as the driver's multi-GPU form has it.
@@ -12,7 +13,9 @@ the batch the banded minimum-control-effort coefficient solve + energy (BASELINE
 batch-minor layout, followed (N > 1) by the all-gather of the per-trajectory costs over RCCL/xGMI
 that the north star names.  Batches shard across ranks (weak scaling, fixed per-GPU batch).
 
-Prints ONE JSON line (rank 0).  `value` is whole-job trajectories/s.  Extra objects:
+Prints ONE JSON line (rank 0).  `value` is whole-job trajectories/s, `ms_per_step` the wall time of one timed step.  A plain
+run sets up, warms up, times the K steps and prints the headline alone; `--full` adds the objects below (every figure that needs
+runs of its own: the other configurations, CPU baselines, per-kernel splits):
   roofline      dominant kernel (k_minco_solve) against HBM: algorithmic bytes / mean kernel time
                 measured with HIP events on the launch stream
   cpu_baseline  the C oracle (classic banded-LU MINCO, oracle/minco_oracle.c) on the host cores
@@ -31,6 +34,12 @@ Prints ONE JSON line (rank 0).  `value` is whole-job trajectories/s.  Extra obje
 
 `--workload config5` makes that evaluation the timed main workload instead (same JSON contract; strong scaling:
 the 32768 trajectories are a fixed total).
+
+`--dump-outputs DIR` writes what the timed path returned to its caller in the last timed step (rank 0's shard), float64, as
+DIR/<name>.npy: `energy` and `coeffs` (rows x trajectories, batch-minor as the library returns them) of the solve; `cost`, `gradP`
+and `gradT` of the config5 evaluation.  Where a batch's coefficients (energies) exceed DUMP_COEFF_BYTES (DUMP_ENERGY_BYTES), a
+fixed seeded sample of the columns is written, in column order.  The inputs are seeded: the same arguments give the same
+inputs from run to run.
 """
 import argparse
 import json
@@ -662,10 +671,11 @@ def allgather_probe(torch, dist, og, device, use_dist, reps=10):
             "allgather_bytes_per_rank": 8 * og.count, "every": og.every, "issued": og.issued}
 
 
-def run_config5(torch, dist, aa, ctx, device, world, rank, use_dist, steps, warmup, total=32768, every=1):
+def run_config5(torch, dist, aa, ctx, device, world, rank, use_dist, steps, warmup, total=32768, every=1, outputs=None):
     """BASELINE configs[4]: `total` x 8-segment min-snap, corridor + velocity / acceleration limit penalties (seed 3),
     contiguous shards over the ranks (remainder to the low ranks), one cost + gradient evaluation of the shard per step
-    (k_minco_solve -> k_piece_grad -> k_minco_propagate) and the all-gather of the costs."""
+    (k_minco_solve -> k_piece_grad -> k_minco_propagate) and the all-gather of the costs.  `outputs` (a dict), if given,
+    receives the shard's cost, gradP and gradT of the last timed step."""
     import numpy as np
     from allocnet_amd.synth import corridor_problem
     from allocnet_amd.distributed import shard_bounds
@@ -718,6 +728,8 @@ def run_config5(torch, dist, aa, ctx, device, world, rank, use_dist, steps, warm
         if og.last is not None and every == 1:
             if not torch.equal(og.recv[og.last][rank * m:rank * m + B], cost[:B]):
                 raise SystemExit("config5: all-gather of costs returned wrong data")
+    if outputs is not None:
+        outputs.update(cost=cost[:B], gradP=gP[:, :B], gradT=gT[:, :B])
     kernel_ms = sum(a.elapsed_time(b) for a, b in ev) / steps
     if os.environ.get("ANET_BENCH_DEBUG"):
         print("config5 per-step event ms:", ["%.3f" % a.elapsed_time(b) for a, b in ev], file=sys.stderr)
@@ -812,6 +824,29 @@ def synth_batch_minor(torch, B, ld, N, c, seed, device):
     wps = pts[1:N].contiguous().view((N - 1) * 3, ld)
     T = 0.5 + 1.5 * torch.rand(N, ld, generator=g, device=device, dtype=f64)
     return head.view(3 * c, ld), tail.view(3 * c, ld), wps, T
+
+
+DUMP_COEFF_BYTES = 24 << 20    # --dump-outputs: the coefficients' share (16 384 trajectories of the 192-row tensor) ...
+DUMP_ENERGY_BYTES = 16 << 20   # ... and the energies' (2^21 trajectories): 40 MiB in all
+
+
+def dump_columns(torch, a, B, max_bytes):
+    """Columns [0, B) of a batch-minor FP64 tensor (rows x ld, or one vector), or, where they exceed `max_bytes`, a fixed seeded
+    sample of as many of them as fit, in column order."""
+    import numpy as np
+    limit = max(1, max_bytes // (8 * a[..., 0].numel()))
+    if B <= limit:
+        return a[..., :B]
+    idx = np.sort(np.random.default_rng(0).choice(B, limit, replace=False))
+    return a[..., torch.from_numpy(idx).to(a.device)]
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every named array as <path>/<name>.npy in float64."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.detach().double().cpu().numpy())
 
 
 LINE_BUDGET = 7000      # the driver keeps a ~8 KB tail of stdout: a longer line loses its head (round 4: config3.b4096, config5)
@@ -924,9 +959,20 @@ def main():
                     help="issue the all-gather of the costs every k-th step only (N > 1; default 1 = every step, the north star)")
     ap.add_argument("--workload", choices=("solve", "config5", "config3", "config4", "qp"), default="solve",
                     help="solve: the headline (configs[1] problem at a saturating batch); config5: BASELINE configs[4]; config3 / "
-                         "config4 / qp: that leg of the default line ALONE, as the line's main workload (one GPU; with --main-only: "
-                         "no CPU baseline, no per-kernel split -- the form tools/profile_leg.sh runs under rocprofv3)")
+                         "config4 / qp: that leg of the --full line ALONE, as the line's main workload (one GPU; without --full "
+                         "or with --main-only: no CPU baseline, no per-kernel split -- the form tools/profile_leg.sh runs under "
+                         "rocprofv3)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline as well: the other configurations, CPU baselines, per-kernel splits")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (solve and config5 workloads)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload not in ("solve", "config5"):
+        ap.error("--dump-outputs is for the solve and config5 workloads")
+    # a plain run measures the main workload alone (as --main-only does); --full adds the rest
+    lean = args.main_only or not args.full
 
     import torch
     import torch.distributed as dist
@@ -961,13 +1007,13 @@ def main():
     ctx = aa.Context(local_rank)
     absorb_runtime_stall(torch, aa, ctx, device)
     if args.workload in ("config3", "config4", "qp"):
-        # one leg of the default line alone (same generator, same timing code: run_config3 / run_config4 / run_qp), so that a
-        # rocprofv3 run holds the kernels of that leg only and profiles/<round>_<leg>_* can be checked against the default line
+        # one leg of the --full line alone (same generator, same timing code: run_config3 / run_config4 / run_qp), so that a
+        # rocprofv3 run holds the kernels of that leg only and profiles/<round>_<leg>_* can be checked against the --full line
         if world != 1:
             raise SystemExit(f"--workload {args.workload} is a single-GPU leg")
-        cpu = not args.no_cpu_baseline and not args.main_only
+        cpu = not args.no_cpu_baseline and not lean
         if args.workload == "config3":
-            leg = run_config3(torch, aa, ctx, device, cpu, 0.25 * args.cpu_seconds, split=not args.main_only)
+            leg = run_config3(torch, aa, ctx, device, cpu, 0.25 * args.cpu_seconds, split=not lean)
             sub = leg["b4096"]
             head_ = {"value": sub["value"], "unit": leg["unit"], "ms_per_step": sub["ms_per_step"], "roofline": sub["roofline"],
                      "workload": "configs[2]: 4096 x 8-segment min-snap, corridor penalties + time-allocation gradients, one cost + "
@@ -978,7 +1024,7 @@ def main():
                      "workload": "configs[3]: 4096 x 16-segment min-jerk, L-BFGS to each problem's own stop, one optimisation of the "
                                  "batch per step", "steps": 1}
         else:
-            leg = run_qp(torch, aa, ctx, device, cpu, 0.5 * args.cpu_seconds, extras=not args.main_only)
+            leg = run_qp(torch, aa, ctx, device, cpu, 0.5 * args.cpu_seconds, extras=not lean)
             sub = leg["snap8"]
             head_ = {"value": sub["value"], "unit": leg["unit"], "ms_per_step": sub["ms_per_batch"], "roofline": sub["roofline"],
                      "workload": "the reference's online solve: 4096 x 8-segment min-snap inequality QPs (interior point), one batch "
@@ -986,14 +1032,18 @@ def main():
         out = {"metric": "MINCO trajectories solved/sec (8-seg min-snap)", "value": head_["value"], "unit": head_["unit"],
                "n_gpus": 1, "steps": head_["steps"], "warmup": args.warmup, "ms_per_step": head_["ms_per_step"],
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-               "config": {"workload": head_["workload"], "leg": args.workload, "main_only": bool(args.main_only)},
+               "config": {"workload": head_["workload"], "leg": args.workload, "main_only": lean},
                "roofline": with_peak(head_["roofline"]), {"config3": "config3", "config4": "config4", "qp": "qp_solve"}[args.workload]: leg}
         if "cpu_baseline" in leg:
             out["cpu_baseline"] = leg["cpu_baseline"]
         print(finalize_line(out), flush=True)
         return
     if args.workload == "config5":
-        c5 = run_config5(torch, dist, aa, ctx, device, world, rank, use_dist, args.steps, args.warmup, every=args.allgather_every)
+        c5_out = {} if args.dump_outputs and rank == 0 else None
+        c5 = run_config5(torch, dist, aa, ctx, device, world, rank, use_dist, args.steps, args.warmup, every=args.allgather_every,
+                         outputs=c5_out)
+        if c5_out is not None:
+            dump_outputs(args.dump_outputs, c5_out)
         if use_dist:
             dist.destroy_process_group()
         if rank != 0:
@@ -1047,12 +1097,17 @@ def main():
         # the gathered costs of the last gather issued must be every rank's costs in rank order
         if og.last is not None and not torch.equal(og.recv[og.last][rank * B:(rank + 1) * B], og.send[og.last][:B]):
             raise SystemExit("all-gather of costs returned wrong data")
+    if args.dump_outputs and rank == 0:
+        # (before the --full legs: they reuse the energy buffer and free the coefficients)
+        last = og.send[(args.steps - 1) & 1]
+        dump_outputs(args.dump_outputs, {"energy": dump_columns(torch, last, B, DUMP_ENERGY_BYTES),
+                                         "coeffs": dump_columns(torch, coeffs, B, DUMP_COEFF_BYTES)})
     kernel_ms = sum(a.elapsed_time(b) for a, b in ev) / args.steps
     ag = allgather_probe(torch, dist, og, device, use_dist)
 
     # every rank takes part in the sharded cost + gradient evaluation (BASELINE configs[4])
     c5 = None
-    if not args.main_only:
+    if not lean:
         del coeffs
         c5 = run_config5(torch, dist, aa, ctx, device, world, rank, use_dist, steps=50, warmup=5, every=args.allgather_every)
         coeffs = torch.empty(N * 3 * D, ld, device=device, dtype=torch.float64)
@@ -1093,7 +1148,7 @@ def main():
     if c5 is not None:
         # (one rank, no process group: the collective's description says nothing -- ranks_seen etc. are in "config")
         out["config5"] = c5 if use_dist else dict(c5, allgather=None)
-    if world == 1 and not args.main_only:
+    if world == 1 and not lean:
         # BASELINE configs[2] and configs[3] are single-GPU configurations: the north-star loop (cost + gradient, L-BFGS)
         del coeffs
         out["config3"] = run_config3(torch, aa, ctx, device, not args.no_cpu_baseline, 0.25 * args.cpu_seconds)

@@ -202,7 +202,7 @@ def test_time_steps_retimes_a_pass_the_runtime_stall_fell_into():
 
 
 def test_leg_workloads_and_their_traffic_lookup(tmp_path, monkeypatch):
-    """`--workload config3|config4|qp` (one leg of the default line alone, the form tools/profile_leg.sh profiles) and
+    """`--workload config3|config4|qp` (one leg of the --full line alone, the form tools/profile_leg.sh profiles) and
     pmc_leg_traffic: WRITE_SIZE + 2 x FETCH_SIZE per launch x launches per step over the kernels of a leg, from
     profiles/<round>_<leg>_pmc.json; the newest file wins; an ambiguous or missing kernel gives None, never a guess."""
     import bench
@@ -229,3 +229,38 @@ def test_leg_workloads_and_their_traffic_lookup(tmp_path, monkeypatch):
     r = bench.fp64_roofline(1e12, 1.0, 1000.0, "k", traffic=2200.0)
     assert r["traffic"] == 2200.0 and abs(r["hbm"]["traffic_over_algorithmic"] - 2.2) < 1e-12
     assert bench.fp64_roofline(1e12, 1.0, 1000.0, "k")["hbm"]["traffic_over_algorithmic"] is None
+
+
+def test_dump_outputs_sampling_and_format(tmp_path):
+    """--dump-outputs: a batch within the byte budget is written whole; above it a fixed seeded sample of the columns, in column
+    order, the same every time; files are float64; the default shapes stay under 64 MB in all."""
+    import numpy as np
+    import torch
+    import bench
+    a = torch.arange(6 * 1000, dtype=torch.float64).view(6, 1000)
+    assert torch.equal(bench.dump_columns(torch, a, 900, 8 * 6 * 900), a[:, :900])
+    s1 = bench.dump_columns(torch, a, 900, 8 * 6 * 100)
+    s2 = bench.dump_columns(torch, a, 900, 8 * 6 * 100)
+    assert s1.shape == (6, 100) and torch.equal(s1, s2)
+    cols = s1[0].long()
+    assert bool((cols[1:] > cols[:-1]).all()) and int(cols[-1]) < 900 and torch.equal(s1, a[:, cols])
+    v = bench.dump_columns(torch, a[0], 1000, 8 * 10)
+    assert v.shape == (10,)
+    bench.dump_outputs(str(tmp_path / "d"), {"x": s1, "y": v.float()})
+    assert np.load(tmp_path / "d" / "x.npy").dtype == np.float64 and np.load(tmp_path / "d" / "y.npy").dtype == np.float64
+    assert bench.DUMP_COEFF_BYTES + bench.DUMP_ENERGY_BYTES <= 64 << 20
+
+
+def test_cli_full_and_dump_options():
+    """--full and --dump-outputs exist; --steps 0 and a dump of a leg workload are refused before anything runs; a plain run
+    gates every sub-leg behind --full."""
+    for args, msg in ((["--steps", "0"], "--steps must be at least 1"),
+                      (["--workload", "qp", "--dump-outputs", "x"], "--dump-outputs is for the solve and config5 workloads")):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=120)
+        assert res.returncode == 2 and msg in res.stderr
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert '"--full"' in src and '"--dump-outputs"' in src
+    assert "lean = args.main_only or not args.full" in src
+    main = src[src.index("def main"):]
+    assert main.index("if not lean:\n        del coeffs") < main.index("run_config5(torch, dist, aa, ctx, device, world, rank, use_dist, steps=50")
+    assert main.index("if world == 1 and not lean:") < main.index('out["config3"] = run_config3')

@@ -1,6 +1,6 @@
 """bench.py itself under the driver's GPU tests: the RCCL code path (a single-rank process group) of both workloads and
-the JSON contract of the default line with the north-star-loop sub-objects, so that a SCALE run is never the first
-execution of that code."""
+the JSON contract of the plain line and of the --full line with the north-star-loop sub-objects, so that a SCALE run is never
+the first execution of that code."""
 import json
 import os
 import subprocess
@@ -67,12 +67,12 @@ def test_gpus_beyond_the_box_is_clamped_not_refused():
 
 
 def test_default_line_carries_the_north_star_loop():
-    """configs[1] headline + config3 / config4 / config5 / qp_solve sub-objects, each with a roofline; the line fits the
+    """`--full`: configs[1] headline + config3 / config4 / config5 / qp_solve sub-objects, each with a roofline; the line fits the
     driver's tail as printed; the whole-batch gradient parity figures of the config3 leg are at rounding level (round 4's
     driver line carried a false 4e-6: the kernel split had overwritten the buffer); short CPU legs."""
     e = dict(os.environ)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-seconds", "2",
-                          "--batch", "65536"], capture_output=True, text=True, timeout=1200, env=e, cwd=ROOT)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--cpu-seconds",
+                          "2", "--batch", "65536"], capture_output=True, text=True, timeout=1200, env=e, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     line = res.stdout.strip().splitlines()[-1]
     assert len(line) <= 7000, len(line)
@@ -94,6 +94,55 @@ def test_default_line_carries_the_north_star_loop():
     assert out["config"]["ranks_seen"] == 1 and out["qp_solve"]["snap8"]["batch"] == 4096
     b1 = out["config1_b1024"]
     assert b1["stream_ms_min_median_max"][0] <= b1["stream_ms_per_step"] <= b1["stream_ms_min_median_max"][2]
+
+
+def test_plain_line_is_the_headline_and_dumps_its_outputs(tmp_path, anet_ctx):
+    """A plain run (no --full) times exactly --steps steps of the headline and launches nothing beside it; --dump-outputs writes
+    the energies and a seeded sample of the coefficients of the last step, FP64, the same from run to run and the same as a direct
+    call of the library on the bench's inputs."""
+    import numpy as np
+    import torch
+    import bench
+    import allocnet_amd as aa
+    B, s, c, N = 65536, 4, 3, 8
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        out = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B), "--dump-outputs", str(d)])
+        for key in KEYS:
+            assert key in out, key
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["dtype"] == "f64"
+        for extra in ("config1_b1024", "config3", "config4", "config5", "qp_solve", "host_api", "cpu_baseline"):
+            assert extra not in out, extra
+        assert sorted(os.listdir(d)) == ["coeffs.npy", "energy.npy"]
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("energy", "coeffs")})
+    for n in ("energy", "coeffs"):
+        assert dumps[0][n].dtype == np.float64 and np.array_equal(dumps[0][n], dumps[1][n]), n
+    energy, coeffs = dumps[0]["energy"], dumps[0]["coeffs"]
+    assert energy.shape == (B,) and np.isfinite(energy).all() and (energy > 0).all()
+    assert coeffs.shape == (N * 3 * 2 * s, bench.DUMP_COEFF_BYTES // (8 * N * 3 * 2 * s))
+    # the bench's own inputs through the library, sampled by the same rule
+    dev = torch.device("cuda", 0)
+    ld = aa.recommended_ld(B)
+    head, tail, wps, T = bench.synth_batch_minor(torch, B, ld, N, c, 0, dev)
+    co, en = aa.minco_solve_dev(head, tail, wps, T, s, c, N, B,
+                                coeffs=torch.empty(N * 3 * 2 * s, ld, device=dev, dtype=torch.float64),
+                                energy=torch.empty(ld, device=dev, dtype=torch.float64), ctx=anet_ctx)
+    np.testing.assert_allclose(energy, en[:B].cpu().numpy(), rtol=1e-12, atol=0)
+    ref = bench.dump_columns(torch, co, B, bench.DUMP_COEFF_BYTES).cpu().numpy()
+    np.testing.assert_allclose(coeffs, ref, rtol=1e-12, atol=1e-12 * np.abs(ref).max())
+
+
+def test_config5_workload_dumps_cost_and_gradients(tmp_path):
+    """--workload config5 --dump-outputs: the cost and both gradients of the last timed evaluation, FP64, one column per
+    trajectory of the 32768."""
+    import numpy as np
+    out = _bench(["--workload", "config5", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == 2 and "config3" not in out
+    cost, gP, gT = (np.load(tmp_path / f"{n}.npy") for n in ("cost", "gradP", "gradT"))
+    assert cost.shape == (32768,) and gP.shape == (3 * 7, 32768) and gT.shape == (8, 32768)
+    for a in (cost, gP, gT):
+        assert a.dtype == np.float64 and np.isfinite(a).all()
 
 
 @pytest.mark.parametrize("leg,key", [("config3", "config3"), ("qp", "qp_solve")])
