@@ -28,15 +28,15 @@
 #include "qp_admm.h"
 #include "qp_ipm.h"
 #include "layout_kernels.h"
+#include "tuning.h"
 
 // ------------------------------------------------------------------------------------------
 // context + error plumbing
 // ------------------------------------------------------------------------------------------
 struct anet_ctx {
   int device = -1;
-  // compute units of the device (hipDeviceAttributeMultiprocessorCount, read once in anet_create): every launch-shape threshold
-  // below was measured on the 256 CUs of an MI355X in SPX mode and is scaled by cus / 256 (per_cu()), so that a partitioned
-  // compute mode (CPX: 32 CUs per logical device) or another part picks its shapes by rounds of workgroups per CU, not by literals
+  // compute units of the device (hipDeviceAttributeMultiprocessorCount, read once in anet_create): the launch-shape thresholds
+  // were measured on the 256 CUs of an MI355X in SPX mode and are scaled by cus / 256 (tuning.h, PerCu)
   int cus = 256;
   hipStream_t stream = nullptr;
   std::string err;
@@ -134,9 +134,6 @@ int ensure_scratch(anet_ctx *ctx, size_t bytes) {
 
 inline int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
-// a batch / group-count threshold measured on 256 compute units, for this context's device
-inline int64_t per_cu(const anet_ctx *ctx, int64_t at_256_cus) { return at_256_cus * (int64_t)ctx->cus / 256; }
-
 // Per-context tables (basis rows of k_piece_grad per (order, res); tables of k_qp_ipm per (order, res, m34)) live until
 // anet_destroy; their number is bounded, and a table whose build fails half-way is released, not leaked.
 constexpr size_t kMaxTablesPerContext = 256;
@@ -166,157 +163,60 @@ void drop_table(double *d, hipEvent_t ready) {
 // collocation solve (minco_dense_kernels.h)
 constexpr double kWideSpread = 50.0;
 
-// Up to this batch the axis-parallel kernel is used (3*B/63 waves still fit the chip's 1024 SIMDs about
-// once); measured crossover on MI355X in DESIGN.md section 4.
-constexpr int64_t kPieceSampleSplitMaxPairs = 16384;  // (trajectory, piece) pairs up to which k_piece_grad splits the samples over waves
-constexpr int64_t kAxisVariantMaxBatchDefault = 16384;
-inline int64_t axis_variant_max_batch(const anet_ctx *ctx) {  // ANET_AXIS_MAX_BATCH overrides (tuning / A-B runs)
-  static const int64_t v = [] {
-    const char *e = getenv("ANET_AXIS_MAX_BATCH");
-    return e ? (int64_t)atoll(e) : (int64_t)-1;
-  }();
-  return v >= 0 ? v : per_cu(ctx, kAxisVariantMaxBatchDefault);
-}
-
+// Small batches (tuning().axis_max_batch) solve and propagate with a lane per (trajectory, axis) -- three times the waves, ~2.4x
+// shorter dependent chains --, larger ones with a lane per trajectory
 template <int S>
 int launch_solve(anet_ctx *ctx, const anet::SolveArgs &a, hipStream_t st) {
-  const dim3 grid((unsigned)((a.B + anet::kSolveBlock - 1) / anet::kSolveBlock));
   const dim3 block(anet::kSolveBlock);
-  // small batches: lane per (trajectory, axis) -- three times the waves, ~2.4x shorter dependent chains
-  if (a.B <= axis_variant_max_batch(ctx)) {
-    const dim3 g3((unsigned)((a.B + 20) / 21));
-    bool done = true;
+  if (a.B <= anet::tuning().axis_max_batch.at(ctx->cus)) {
     // (exact shapes with an even number of pieces, batches that leave SIMDs empty: the chain from both ends, two lanes per axis)
-    static const int64_t two_env = [] { const char *e = getenv("ANET_AXIS_TWO_MAX_BATCH"); return e ? (int64_t)atoll(e) : (int64_t)-1; }();
-    const int64_t two_max = two_env >= 0 ? two_env : per_cu(ctx, 4096);
-    const dim3 g6((unsigned)((a.B + 9) / 10));
-    if (a.B <= two_max && a.c == 3 && ((S == 4 && a.N == 8) || (S == 3 && a.N == 16))) {
+    if (a.B <= anet::tuning().axis_two_max_batch.at(ctx->cus) && a.c == 3 && ((S == 4 && a.N == 8) || (S == 3 && a.N == 16))) {
+      const dim3 g6((unsigned)((a.B + 9) / 10));
       if constexpr (S == 4) hipLaunchKernelGGL((anet::k_minco_solve_axis_two<4, 8, 2>), g6, block, 0, st, a);
       else if constexpr (S == 3) hipLaunchKernelGGL((anet::k_minco_solve_axis_two<3, 16, 2>), g6, block, 0, st, a);
-      ANET_HIP(ctx, hipGetLastError());
-      return ANET_OK;
-    }
-    if constexpr (S == 4) {
-      if (a.N == 8 && a.c == 3) hipLaunchKernelGGL((anet::k_minco_solve_axis<4, 8, true, 2>), g3, block, 0, st, a);
-      else if (a.N == 8 && a.c == 4) hipLaunchKernelGGL((anet::k_minco_solve_axis<4, 8, true, 3>), g3, block, 0, st, a);
-      else if (a.N == 5 && a.c == 3) hipLaunchKernelGGL((anet::k_minco_solve_axis<4, 5, true, 2>), g3, block, 0, st, a);
-      else done = false;
-    } else if constexpr (S == 3) {
-      if (a.N == 16 && a.c == 3) hipLaunchKernelGGL((anet::k_minco_solve_axis<3, 16, true, 2>), g3, block, 0, st, a);
-      else if (a.N == 5 && a.c == 3) hipLaunchKernelGGL((anet::k_minco_solve_axis<3, 5, true, 2>), g3, block, 0, st, a);
-      else done = false;
     } else {
-      done = false;
+      const dim3 g3((unsigned)((a.B + 20) / 21));
+      anet::with_minco_shape<S>(a.N, a.c, [&](auto sh) {
+        using Sh = decltype(sh);
+        hipLaunchKernelGGL((anet::k_minco_solve_axis<S, Sh::NB, Sh::EXACT, Sh::NPC>), g3, block, 0, st, a);
+      });
     }
-    if (!done) {
-      if (a.N <= 4) hipLaunchKernelGGL((anet::k_minco_solve_axis<S, 4>), g3, block, 0, st, a);
-      else if (a.N <= 8) hipLaunchKernelGGL((anet::k_minco_solve_axis<S, 8>), g3, block, 0, st, a);
-      else hipLaunchKernelGGL((anet::k_minco_solve_axis<S, 16>), g3, block, 0, st, a);
-    }
-    ANET_HIP(ctx, hipGetLastError());
-    return ANET_OK;
+  } else {
+    const dim3 grid((unsigned)((a.B + anet::kSolveBlock - 1) / anet::kSolveBlock));
+    anet::with_minco_shape<S>(a.N, a.c, [&](auto sh) {
+      using Sh = decltype(sh);
+      hipLaunchKernelGGL((anet::k_minco_solve<S, Sh::NB, Sh::EXACT, Sh::NPC>), grid, block, 0, st, a);
+    });
   }
-  // fully specialised instantiations for the shapes the benchmarks and the reference use
-  if constexpr (S == 4) {
-    if (a.N == 8 && a.c == 3) {
-      hipLaunchKernelGGL((anet::k_minco_solve<4, 8, true, 2>), grid, block, 0, st, a);
-      ANET_HIP(ctx, hipGetLastError());
-      return ANET_OK;
-    }
-    if (a.N == 8 && a.c == 4) {
-      hipLaunchKernelGGL((anet::k_minco_solve<4, 8, true, 3>), grid, block, 0, st, a);
-      ANET_HIP(ctx, hipGetLastError());
-      return ANET_OK;
-    }
-    if (a.N == 5 && a.c == 3) {  // the planner's own shape: five pieces (learning_planner.hpp:179), PVA ends
-      hipLaunchKernelGGL((anet::k_minco_solve<4, 5, true, 2>), grid, block, 0, st, a);
-      ANET_HIP(ctx, hipGetLastError());
-      return ANET_OK;
-    }
-  }
-  if constexpr (S == 3) {
-    if (a.N == 16 && a.c == 3) {
-      hipLaunchKernelGGL((anet::k_minco_solve<3, 16, true, 2>), grid, block, 0, st, a);
-      ANET_HIP(ctx, hipGetLastError());
-      return ANET_OK;
-    }
-    if (a.N == 5 && a.c == 3) {
-      hipLaunchKernelGGL((anet::k_minco_solve<3, 5, true, 2>), grid, block, 0, st, a);
-      ANET_HIP(ctx, hipGetLastError());
-      return ANET_OK;
-    }
-  }
-  if (a.N <= 4)
-    hipLaunchKernelGGL((anet::k_minco_solve<S, 4>), grid, block, 0, st, a);
-  else if (a.N <= 8)
-    hipLaunchKernelGGL((anet::k_minco_solve<S, 8>), grid, block, 0, st, a);
-  else
-    hipLaunchKernelGGL((anet::k_minco_solve<S, 16>), grid, block, 0, st, a);
   ANET_HIP(ctx, hipGetLastError());
   return ANET_OK;
 }
 
+// (no fully specialised instantiation for 8-piece snap with c = 4)
 template <int S>
 static int launch_sample(anet_ctx *ctx, const anet::SampleArgs &a, hipStream_t st) {
   const dim3 grid((unsigned)((a.B + anet::kSolveBlock - 1) / anet::kSolveBlock)), block(anet::kSolveBlock);
-  bool done = true;
-  if constexpr (S == 4) {
-    if (a.N == 8 && a.c == 3) hipLaunchKernelGGL((anet::k_minco_sample<4, 8, true, 2>), grid, block, 0, st, a);
-    else if (a.N == 5 && a.c == 3) hipLaunchKernelGGL((anet::k_minco_sample<4, 5, true, 2>), grid, block, 0, st, a);
-    else done = false;
-  } else if constexpr (S == 3) {
-    if (a.N == 16 && a.c == 3) hipLaunchKernelGGL((anet::k_minco_sample<3, 16, true, 2>), grid, block, 0, st, a);
-    else if (a.N == 5 && a.c == 3) hipLaunchKernelGGL((anet::k_minco_sample<3, 5, true, 2>), grid, block, 0, st, a);
-    else done = false;
-  } else {
-    done = false;
-  }
-  if (!done) {
-    if (a.N <= 4) hipLaunchKernelGGL((anet::k_minco_sample<S, 4>), grid, block, 0, st, a);
-    else if (a.N <= 8) hipLaunchKernelGGL((anet::k_minco_sample<S, 8>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((anet::k_minco_sample<S, 16>), grid, block, 0, st, a);
-  }
+  anet::with_minco_shape<S, false>(a.N, a.c, [&](auto sh) {
+    using Sh = decltype(sh);
+    hipLaunchKernelGGL((anet::k_minco_sample<S, Sh::NB, Sh::EXACT, Sh::NPC>), grid, block, 0, st, a);
+  });
   ANET_HIP(ctx, hipGetLastError());
   return ANET_OK;
 }
 
 template <int S>
 int launch_prop(anet_ctx *ctx, const anet::PropArgs &a, hipStream_t st) {
-  const dim3 grid((unsigned)((a.B + anet::kSolveBlock - 1) / anet::kSolveBlock));
   const dim3 block(anet::kSolveBlock);
-  if (a.B <= axis_variant_max_batch(ctx)) {  // same small-batch split as launch_solve
+  if (a.B <= anet::tuning().axis_max_batch.at(ctx->cus)) {  // same small-batch split as launch_solve
     const dim3 g3((unsigned)((a.B + 20) / 21));
     anet::launch_propagate_axis(S, a, g3, block, st);  // (piece_grad_unit.hip: scheduled for ILP)
-    ANET_HIP(ctx, hipGetLastError());
-    return ANET_OK;
+  } else {
+    const dim3 grid((unsigned)((a.B + anet::kSolveBlock - 1) / anet::kSolveBlock));
+    anet::with_minco_shape<S>(a.N, a.c, [&](auto sh) {
+      using Sh = decltype(sh);
+      hipLaunchKernelGGL((anet::k_minco_propagate<S, Sh::NB, Sh::EXACT, Sh::NPC>), grid, block, 0, st, a);
+    });
   }
-  if constexpr (S == 4) {
-    if (a.N == 8 && (a.c == 3 || a.c == 4)) {
-      if (a.c == 3) hipLaunchKernelGGL((anet::k_minco_propagate<4, 8, true, 2>), grid, block, 0, st, a);
-      else hipLaunchKernelGGL((anet::k_minco_propagate<4, 8, true, 3>), grid, block, 0, st, a);
-      ANET_HIP(ctx, hipGetLastError());
-      return ANET_OK;
-    }
-  }
-  if constexpr (S == 3) {
-    if (a.N == 16 && a.c == 3) {
-      hipLaunchKernelGGL((anet::k_minco_propagate<3, 16, true, 2>), grid, block, 0, st, a);
-      ANET_HIP(ctx, hipGetLastError());
-      return ANET_OK;
-    }
-  }
-  if (a.N == 5 && a.c == 3 && S >= 3) {  // the planner's shape
-    if constexpr (S == 4) hipLaunchKernelGGL((anet::k_minco_propagate<4, 5, true, 2>), grid, block, 0, st, a);
-    else if constexpr (S == 3) hipLaunchKernelGGL((anet::k_minco_propagate<3, 5, true, 2>), grid, block, 0, st, a);
-    ANET_HIP(ctx, hipGetLastError());
-    return ANET_OK;
-  }
-  if (a.N <= 4)
-    hipLaunchKernelGGL((anet::k_minco_propagate<S, 4>), grid, block, 0, st, a);
-  else if (a.N <= 8)
-    hipLaunchKernelGGL((anet::k_minco_propagate<S, 8>), grid, block, 0, st, a);
-  else
-    hipLaunchKernelGGL((anet::k_minco_propagate<S, 16>), grid, block, 0, st, a);
   ANET_HIP(ctx, hipGetLastError());
   return ANET_OK;
 }
@@ -351,18 +251,6 @@ static anet::LbfgsP to_kernel_params(const anet_lbfgs_params &p) {
                       p.min_step, p.max_step, p.f_dec_coeff, p.s_curv_coeff, p.cautious_factor, p.machine_prec};
 }
 
-// One wave per problem at every batch size: at 131072 x 29 variables the lane-per-problem update kernel took 1.67 ms
-// per tick (three times the objective evaluation), the wave kernel 0.4 ms.  The lane kernel remains for n > 128 or
-// mem_size > 64.
-constexpr int64_t kLbfgsWaveMaxBatchDefault = INT64_MAX;
-inline int64_t lbfgs_wave_max_batch() {  // ANET_LBFGS_WAVE_MAX_BATCH overrides (tuning / A-B runs)
-  static const int64_t v = [] {
-    const char *e = getenv("ANET_LBFGS_WAVE_MAX_BATCH");
-    return e ? (int64_t)atoll(e) : kLbfgsWaveMaxBatchDefault;
-  }();
-  return v;
-}
-
 static int ensure_counter(anet_ctx *ctx) {
   if (!ctx->d_counter) ANET_HIP(ctx, hipMalloc((void **)&ctx->d_counter, sizeof(int)));
   if (!ctx->h_counter) ANET_HIP(ctx, hipHostMalloc((void **)&ctx->h_counter, 2 * sizeof(int), hipHostMallocDefault));
@@ -386,9 +274,10 @@ static int lbfgs_drive(anet_ctx *ctx, LbfgsLayout &L, int64_t B, const anet_lbfg
     ANET_HIP(ctx, hipMemsetAsync(L.is, 0, sizeof(int) * anet::IS_COUNT_ * L.ld, st));
     ANET_HIP(ctx, hipMemsetAsync(L.ds, 0, sizeof(double) * anet::DS_COUNT_ * L.ld, st));
   }
-  // one wave per problem (DPP reductions, internal vectors problem-major) whenever the problem fits a wave's
-  // registers; otherwise one lane per problem (internal vectors batch-minor)
-  const bool wave = B <= lbfgs_wave_max_batch() && L.n <= 128 && prm.mem_size <= 64;
+  // one wave per problem (DPP reductions, internal vectors problem-major) whenever the problem fits a wave's registers, at every
+  // batch size -- at 131072 x 29 variables the lane-per-problem update kernel took 1.67 ms per tick (three times the objective
+  // evaluation), the wave kernel 0.4 ms --; otherwise one lane per problem (internal vectors batch-minor)
+  const bool wave = L.n <= 128 && prm.mem_size <= 64;
   anet::LbfgsArgs a{L.n, B, L.ld, L.x, L.g, L.xp, L.gp, L.d, L.lm_s, L.lm_y, L.lm_ys, L.lm_alpha, L.pf, L.ds,
                     L.feval, L.is, to_kernel_params(prm), nullptr, wave ? 1 : L.ld, wave ? L.n : 1, map_T, map_nw,
                     sb_on, map_nw, sb_xmin, (const int *)cancel};
@@ -407,8 +296,7 @@ static int lbfgs_drive(anet_ctx *ctx, LbfgsLayout &L, int64_t B, const anet_lbfg
       };
       dim3 gw, bw;
       const bool one = L.n <= 64;  // one variable per lane: half the registers
-      static const int half_ok = [] { const char *e = getenv("ANET_LBFGS_HALF_WAVE"); return e ? atoi(e) : 1; }();
-      if (a.p.mem_size <= 8 && L.n <= 32 && half_ok) {  // two problems per wave
+      if (a.p.mem_size <= 8 && L.n <= 32) {  // two problems per wave
         const int waves = anet::LbfgsWaveShape<8>::kWaves;
         gw = dim3((unsigned)((B + 2 * waves - 1) / (2 * waves)));
         bw = dim3(64u * waves);
@@ -478,6 +366,49 @@ __global__ void __launch_bounds__(1024) k_order_scan(int *hist) {  // exclusive 
 __global__ void k_order_scatter(const int *counts, int64_t B, int *hist, int *order, int shift) {
   const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (b < B) order[atomicAdd(&hist[order_bucket(counts[b], shift)], 1)] = (int)b;
+}
+
+static int launch_order_impl(anet_ctx *ctx, int64_t batch, const int32_t *counts, int32_t *launch_order, int32_t *work,
+                             void *stream, int shift) {
+  ANET_ON_DEVICE(ctx);
+  if (batch < 0 || batch > 0x7fffffff) return fail(ctx, ANET_ERR_INVALID, "anet_launch_order_from_counts: bad batch");
+  if (batch == 0) return ANET_OK;
+  if (!counts || !launch_order || !work) return fail(ctx, ANET_ERR_INVALID, "anet_launch_order_from_counts_dev: NULL pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)((batch + 255) / 256)), block(256);
+  ANET_HIP(ctx, hipMemsetAsync(work, 0, sizeof(int) * kOrderBuckets, st));
+  hipLaunchKernelGGL(k_order_hist, grid, block, 0, st, counts, batch, work, shift);
+  hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(1024), 0, st, work);
+  hipLaunchKernelGGL(k_order_scatter, grid, block, 0, st, counts, batch, work, launch_order, shift);
+  ANET_HIP(ctx, hipGetLastError());
+  return ANET_OK;
+}
+
+// The tail of the workspace of a solve that can run in two launches (the one-launch L-BFGS, the interior-point QP): the parked
+// state of every problem (`per` doubles each), then its score and the order of the second launch (int32 rows of ld, each padded
+// to whole doubles) and the bins of the counting sort.  doubles() is what the _workspace functions add for it, carve() is how
+// the _dev_impls cut it.
+struct ResumeTail {
+  int64_t per, ld;
+  double *cont;
+  int32_t *score, *order, *bins;
+  static int64_t doubles(int64_t per, int64_t ld) { return per * ld + ld + 2 + kOrderBuckets / 2; }
+  void carve(double *w) {
+    cont = w;
+    score = (int32_t *)(cont + per * ld);
+    order = score + ld + (ld & 1);
+    bins = order + ld + (ld & 1);
+  }
+};
+
+// Between the two launches of a two-launch solve, whose first launch parked the unfinished problems in t.cont: score them
+// (score(t.score) enqueues the solver's score kernel), counting-sort the scores into the order of the second launch, longest-
+// expected first, and enqueue that launch (resume(t.order)).
+template <class Score, class Resume>
+static int resume_parked(anet_ctx *ctx, int64_t batch, const ResumeTail &t, hipStream_t st, Score &&score, Resume &&resume) {
+  score(t.score);
+  const int rc = launch_order_impl(ctx, batch, t.score, t.order, t.bins, st, 0);
+  return rc ? rc : resume(t.order);
 }
 
 // 1 where the durations of a trajectory spread over more than min_spread (max T > min_spread min T)
@@ -1039,20 +970,12 @@ static int basis_table(anet_ctx *ctx, int s, int res, hipStream_t st, const doub
 // The large-batch penalty kernel with the basis-table contractions on the FP64 matrix instructions (csrc/piece_grad_mx.h): built for
 // res = 20, orders 3 and 4 (131 072 x 8 snap pieces: 295 us against 344; 65 536 x 16 jerk pieces: 287 against 296 -- six coefficients
 // fill three quarters of the instructions' k and column tiles --, profiles/r06_piece_grad_mx.txt).  ANET_PG_MX=0: never (A-B runs).
-static int anet_piece_grad_mx_res() { return 20; }
-static bool piece_grad_mx_enabled() {
-  static const int v = [] { const char *e = getenv("ANET_PG_MX"); return e ? atoi(e) : 1; }();
-  return v != 0;
-}
-
 // The launch shape of the penalty / energy-gradient kernel (launch_piece_grad): 0 a lane per (trajectory, piece); 1 two lanes per
 // pair (small batches); 2 two lanes and the samples over a workgroup's four waves (fewest pairs); 3 k_piece_grad_mx
 static int piece_grad_shape(anet_ctx *ctx, int s, int n_pieces, int64_t batch, const anet_penalty *pen) {
-  // ANET_PIECE_SW_MAX_PAIRS overrides (tuning / A-B runs)
-  static const int64_t sw_env = [] { const char *e = getenv("ANET_PIECE_SW_MAX_PAIRS"); return e ? (int64_t)atoll(e) : (int64_t)-1; }();
-  const int64_t sw_max_pairs = sw_env >= 0 ? sw_env : per_cu(ctx, kPieceSampleSplitMaxPairs);
-  if (pen && batch <= axis_variant_max_batch(ctx)) return batch * n_pieces <= sw_max_pairs ? 2 : 1;
-  if (pen && pen->res == anet_piece_grad_mx_res() && (s == 3 || s == 4) && piece_grad_mx_enabled()) return 3;
+  const anet::Tuning &t = anet::tuning();
+  if (pen && batch <= t.axis_max_batch.at(ctx->cus)) return batch * n_pieces <= t.piece_sw_max_pairs.at(ctx->cus) ? 2 : 1;
+  if (pen && pen->res == anet::kMxRes && (s == 3 || s == 4) && t.pg_mx) return 3;
   return 0;
 }
 
@@ -1129,12 +1052,10 @@ static bool cost_grad_in_one_launch(const anet_ctx *ctx, int s, int c, int n_pie
   // a round of groups costs 17 us instead of 27 and the crossover moves out -- 16 384 x 8-seg snap (four rounds) 68.7 us against 102.9,
   // 24 576 (six) 100.5 / 107.4, 32 768 (eight) 133.4 / 125.5: SIX rounds; 16 384 x 16-seg jerk (eight rounds of groups of 8) 131.4 / 150.6:
   // EIGHT.  (ANET_FUSED_MAX_GROUPS overrides; 0 disables.)
-  static const int64_t fused_groups_env = [] { const char *e = getenv("ANET_FUSED_MAX_GROUPS"); return e ? (int64_t)atoll(e) : (int64_t)-1; }();
-  static const int fused_mx_env = [] { const char *e = getenv("ANET_FUSED_MX"); return e ? atoi(e) : 1; }();
-  const bool mx = fused_mx_env && pen && pen->res == anet_piece_grad_mx_res() && c == 3 &&
-                  ((s == 4 && n_pieces == 8) || (s == 3 && n_pieces == 16));
+  const bool mx = pen && anet::fused_phase2_mx(s, c, n_pieces, pen->res);
   const int rounds = mx ? (n_pieces <= 8 ? 6 : 8) : (n_pieces <= 8 ? 3 : 2);
-  const int64_t fused_max_groups = fused_groups_env >= 0 ? fused_groups_env : rounds * (int64_t)ctx->cus;
+  const int64_t env_groups = anet::tuning().fused_max_groups;
+  const int64_t fused_max_groups = env_groups >= 0 ? env_groups : rounds * (int64_t)ctx->cus;
   const int fg = pen ? anet::cost_grad_fused_group(s, n_pieces) : 0;
   return fg > 0 && (batch + fg - 1) / fg <= fused_max_groups && pen->res <= anet::kFusedMaxRes;
 }
@@ -1168,7 +1089,7 @@ static int cost_grad_dev_impl(anet_ctx *ctx, int s, int c, int n_pieces, int64_t
     if (anet::launch_cost_grad_fused(s, fa, tab, (hipStream_t)stream, ctx->cus)) {
       ANET_HIP(ctx, hipGetLastError());
 #ifdef ANET_FUSED_PROF
-      if (getenv("ANET_FUSED_PROF_PRINT")) {
+      if (anet::env_set("ANET_FUSED_PROF_PRINT")) {
         long long h[16];
         ANET_HIP(ctx, hipMemcpyAsync(h, d_fprof, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)stream));
         ANET_HIP(ctx, hipStreamSynchronize((hipStream_t)stream));
@@ -1342,7 +1263,7 @@ int anet_lbfgs_mvie(anet_ctx *ctx, int64_t batch, int M, const double *A, double
   ANET_HIP(ctx, hipMemcpyAsync(L.x, d_x0, sizeof(double) * n * st.ld, hipMemcpyDeviceToDevice, s0));
   anet::MvieArgs ma{d_A, L.x, L.feval, L.g, L.is, batch, st.ld, M, smooth_eps, penalty_wt};
   const dim3 grid((unsigned)((batch + 63) / 64)), block(64);
-  if (batch <= lbfgs_wave_max_batch() && params->mem_size <= 64) {
+  if (params->mem_size <= 64) {
     // one wave per problem, the whole optimisation in one launch (k_lbfgs_mvie_persistent)
     ANET_HIP(ctx, hipMemsetAsync(L.is, 0, sizeof(int) * anet::IS_COUNT_ * L.ld, s0));
     ANET_HIP(ctx, hipMemsetAsync(L.ds, 0, sizeof(double) * anet::DS_COUNT_ * L.ld, s0));
@@ -1352,7 +1273,7 @@ int anet_lbfgs_mvie(anet_ctx *ctx, int64_t batch, int M, const double *A, double
       hipLaunchKernelGGL(kernel, dim3((unsigned)((batch + waves - 1) / waves)), dim3(64u * waves), 0, s0, la, ma, max_evals);
     };
     // everything in registers when it fits (<= 128 rows, mem_size <= 20, past <= 64); else the state goes through memory
-    const bool resident = M <= 128 && m <= 20 && params->past <= 64 && !getenv("ANET_MVIE_STATE_IN_MEMORY");
+    const bool resident = M <= 128 && m <= 20 && params->past <= 64 && !anet::env_set(anet::Tuning::mvie_state_in_memory);
     if (resident && m <= 8 && M <= 64) launch(anet::k_lbfgs_mvie_resident<8, 1>, 1);
     else if (resident && m <= 8) launch(anet::k_lbfgs_mvie_resident<8, 2>, 1);
     else if (resident && M <= 64) launch(anet::k_lbfgs_mvie_resident<20, 1>, 1);
@@ -1597,7 +1518,7 @@ int anet_firi_var_dev(anet_ctx *ctx, int64_t batch, int n_bd, int max_points, in
     ANET_HIP(ctx, hipGetLastError());
     {  // the whole MVIE optimisation in one launch, one wave per corridor; rows and optimiser state in registers when they fit
       constexpr int kw = anet::LbfgsWaveShape<20>::kWaves;
-      const bool in_memory = getenv("ANET_MVIE_STATE_IN_MEMORY") != nullptr;  // A/B switch (tools/README.md)
+      const bool in_memory = anet::env_set(anet::Tuning::mvie_state_in_memory);
       if (!in_memory && H <= 64 && lp.mem_size <= 20 && lp.past <= 64)
         hipLaunchKernelGGL((anet::k_lbfgs_mvie_resident<20, 1>), dim3((unsigned)batch), dim3(64), 0, st, la, ev, P.mvie_max_evals);
       else if (!in_memory && H <= 128 && lp.mem_size <= 20 && lp.past <= 64)
@@ -1678,13 +1599,12 @@ int anet_polytope_depth_dev(anet_ctx *ctx, int64_t batch, int max_rows, const do
   if (batch == 0) return ANET_OK;
   if (!hpoly || !depth) return fail(ctx, ANET_ERR_INVALID, "anet_polytope_depth_dev: NULL pointer");
   // active-set ascent, one lane per polytope, certified; what it cannot certify (NaN) goes to the vertex enumeration
-  const bool enumerate_all = getenv("ANET_POLYTOPE_DEPTH_ENUMERATE") != nullptr;  // A/B switch
+  const bool enumerate_all = anet::env_set(anet::Tuning::polytope_depth_enumerate);
   anet::DepthArgs a{hpoly, depth, point, batch, max_rows, normalise ? 1 : 0, enumerate_all ? 0 : 1};
   if (!enumerate_all) {
     hipLaunchKernelGGL(anet::k_polytope_depth_simplex, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
     ANET_HIP(ctx, hipGetLastError());
   }
-  if (getenv("ANET_POLYTOPE_DEPTH_NO_FALLBACK")) return ANET_OK;  // diagnostics: NaN marks what the ascent did not certify
   hipLaunchKernelGGL(anet::k_polytope_depth, dim3((unsigned)batch), dim3(256), sizeof(double) * max_rows * 4, (hipStream_t)stream, a);
   ANET_HIP(ctx, hipGetLastError());
   return ANET_OK;
@@ -1710,14 +1630,6 @@ int anet_polytope_depth(anet_ctx *ctx, int64_t batch, int max_rows, const double
   return ANET_OK;
 }
 
-// Thresholds of the two-launch form of the one-launch L-BFGS (lbfgs_minco_dev_impl; the environment overrides are for A/B runs)
-static int lbfgs_split_evals() { static const int v = [] { const char *e = getenv("ANET_LBFGS_SPLIT_EVALS"); return e ? atoi(e) : 1000; }(); return v; }
-static int64_t lbfgs_split_min_batch(const anet_ctx *ctx) {  // (4096 problems on 256 CUs = twice the resident waves)
-  static const int64_t v = [] { const char *e = getenv("ANET_LBFGS_SPLIT_MIN_BATCH"); return e ? (int64_t)atoll(e) : (int64_t)-1; }();
-  return v >= 0 ? v : per_cu(ctx, 4096);
-}
-static int lbfgs_split_min_vars() { static const int v = [] { const char *e = getenv("ANET_LBFGS_SPLIT_MIN_VARS"); return e ? atoi(e) : 36; }(); return v; }
-
 int64_t anet_lbfgs_minco_workspace(int s, int n_pieces, int64_t ld, const anet_lbfgs_params *params) {
   if (!params || params->mem_size <= 0) return -1;
   const int n = 3 * (n_pieces - 1) + n_pieces;
@@ -1726,10 +1638,9 @@ int64_t anet_lbfgs_minco_workspace(int s, int n_pieces, int64_t ld, const anet_l
   int64_t w = LbfgsLayout::doubles(n, params->mem_size, npf, ld) + anet_minco_cost_grad_workspace(s, n_pieces, ld) + (int64_t)n * ld;
   // ... then, where the two-launch form of the one-launch shape can run (enough variables; whether a BATCH takes it is the
   // context's decision -- lbfgs_minco_dev_impl, by the device's compute units -- and does not enter the size: a workspace of
-  // this size is enough for either form at any batch <= ld), the parked optimisers, their scores and the order of the second
-  // launch (int32 each) and the bins of the counting sort
-  if (lbfgs_split_evals() > 1 && n >= lbfgs_split_min_vars())
-    w += (int64_t)anet::kPersistContDoubles * ld + ld + 2 + kOrderBuckets / 2;
+  // this size is enough for either form at any batch <= ld), the tail the two launches hand the parked optimisers over in
+  if (anet::tuning().lbfgs_split_evals > 1 && n >= anet::tuning().lbfgs_split_min_vars)
+    w += ResumeTail::doubles(anet::kPersistContDoubles, ld);
   return w;
 }
 
@@ -1750,22 +1661,6 @@ __global__ void k_lbfgs_resume_score(const int *is, const double *cont, int64_t 
     sc = (int)fmin(fmax(v, 1.0), 4000.0);
   }
   score[b] = sc;
-}
-
-static int launch_order_impl(anet_ctx *ctx, int64_t batch, const int32_t *counts, int32_t *launch_order, int32_t *work,
-                             void *stream, int shift) {
-  ANET_ON_DEVICE(ctx);
-  if (batch < 0 || batch > 0x7fffffff) return fail(ctx, ANET_ERR_INVALID, "anet_launch_order_from_counts: bad batch");
-  if (batch == 0) return ANET_OK;
-  if (!counts || !launch_order || !work) return fail(ctx, ANET_ERR_INVALID, "anet_launch_order_from_counts_dev: NULL pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)((batch + 255) / 256)), block(256);
-  ANET_HIP(ctx, hipMemsetAsync(work, 0, sizeof(int) * kOrderBuckets, st));
-  hipLaunchKernelGGL(k_order_hist, grid, block, 0, st, counts, batch, work, shift);
-  hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(1024), 0, st, work);
-  hipLaunchKernelGGL(k_order_scatter, grid, block, 0, st, counts, batch, work, launch_order, shift);
-  ANET_HIP(ctx, hipGetLastError());
-  return ANET_OK;
 }
 
 int anet_launch_order_from_counts_dev(anet_ctx *ctx, int64_t batch, const int32_t *counts, int32_t *launch_order,
@@ -1856,15 +1751,10 @@ static int lbfgs_minco_dev_impl(anet_ctx *ctx, int s, int c, int n_pieces, int64
   // evaluation kernels (all 64 lanes busy in the chains) have up to twice the throughput per evaluation STEP at batches
   // of 10^5, but a run to convergence is as long as its slowest member times the whole batch there: 131072 x 8-segment
   // snap 2.3 s in one launch against 4.1 s in lockstep, 131072 x 16-segment jerk 3.5 s against 10.0 s.  So one launch
-  // at any batch (ANET_LBFGS_PERSISTENT_MAX_BATCH caps it for A/B runs); callers with a small fixed evaluation budget
-  // at a huge batch ask for the lockstep shape (ANET_OPT_LOCKSTEP).
-  static const int64_t persist_max_batch = [] {
-    const char *e = getenv("ANET_LBFGS_PERSISTENT_MAX_BATCH");
-    return e ? (int64_t)atoll(e) : (int64_t)0x7fffffff;
-  }();
+  // at any batch; callers with a small fixed evaluation budget at a huge batch ask for the lockstep shape (ANET_OPT_LOCKSTEP).
   const int Mrows = (pen && hpolys) ? pen->poly_rows : 0;
   const size_t row_bytes = sizeof(double) * anet::persist_lds_row_doubles(N, Mrows);
-  if (!(opt_flags & ANET_OPT_LOCKSTEP) && batch <= persist_max_batch && (s == 3 || s == 4) && n <= 64 &&
+  if (!(opt_flags & ANET_OPT_LOCKSTEP) && (s == 3 || s == 4) && n <= 64 &&
       params->mem_size <= 8 && params->past <= 64) {
     anet::PersistArgs pa{};
     pa.head = head; pa.tail = tail; pa.wps = wps; pa.T = T; pa.hpolys = Mrows ? hpolys : nullptr;
@@ -1891,65 +1781,58 @@ static int lbfgs_minco_dev_impl(anet_ctx *ctx, int s, int c, int n_pieces, int64
     // evaluations (equally long waves: no late starters), the second resumes the unfinished ones longest-expected first.  The
     // batch of BASELINE configs[3] (4096 problems, 300..7400 evaluations) otherwise ends with whichever long problem happened to
     // start in the second round: 0.160 s against 0.117 s with the problems longest first by their true counts.
-    const int split_evals = lbfgs_split_evals();
-    // (a SECOND park / re-sort, measured in round 5 and left off: profiles/r05_lbfgs_second_park.txt -- every stage boundary is a
-    //  barrier for the whole batch, and what the better order of the third stage gains is less than what the second stage's own
-    //  tail loses: configs[3] 136 -> 147 / 157 / 165 ms with the second boundary at 2000 / 2500 / 3000 evaluations)
-    static const int split_evals2 = [] { const char *e = getenv("ANET_LBFGS_SPLIT_EVALS2"); return e ? atoi(e) : 0; }();
-    const int64_t split_min_batch = lbfgs_split_min_batch(ctx);
     // ... where it was measured to pay (tools/time_lbfgs_batch.py, 4096 problems unless noted, one launch -> two): 16 jerk pieces
     // 165 -> 140 ms (bench: 0.169 -> 0.133 s), 16 snap pieces 424 -> 389, 12 jerk pieces 107 -> 98, 10 jerk pieces 79 -> 77, 16 jerk
     // pieces x 8192 235 -> 216, x 16384 415 -> 403, x 3072 no change; 8 snap pieces 102 -> 100..109, 5 jerk pieces 23.5 -> 25, 5
     // snap pieces 37 -> 39 (their runs are a few hundred evaluations long: the split point lies behind most of them, and at 250..700
     // evaluations the parked state does not tell the long problems yet).  Hence: problems of at least 36 variables (ten pieces).
-    const int split_min_vars = lbfgs_split_min_vars();
-    const bool two_launches = split_evals > 1 && batch >= split_min_batch && n >= split_min_vars && !launch_order && max_evals > split_evals;
-    double *cont = w_gP + (int64_t)n * ld;
-    int32_t *score = (int32_t *)(cont + (int64_t)anet::kPersistContDoubles * ld);
-    int32_t *order2 = score + ld + (ld & 1);
-    int32_t *bins = order2 + ld + (ld & 1);
-    bool order_failed = false;
-    auto launch = [&](auto kernel, size_t fixed_bytes) {
+    // (A SECOND park / re-sort was measured in round 5 and not kept: profiles/r05_lbfgs_second_park.txt -- every stage boundary is
+    //  a barrier for the whole batch, and what the better order of a third stage gains is less than what the second stage's own
+    //  tail loses: configs[3] 136 -> 147 / 157 / 165 ms with the second boundary at 2000 / 2500 / 3000 evaluations.)
+    const anet::Tuning &t = anet::tuning();
+    const int split_evals = t.lbfgs_split_evals;
+    const bool two_launches = split_evals > 1 && batch >= t.lbfgs_split_min_batch.at(ctx->cus) && n >= t.lbfgs_split_min_vars &&
+                              !launch_order && max_evals > split_evals;
+    ResumeTail rt{anet::kPersistContDoubles, ld};
+    rt.carve(w_gP + (int64_t)n * ld);
+    auto launch = [&](auto kernel, size_t fixed_bytes) -> int {
+      const size_t lds = fixed_bytes + row_bytes;
       if (!two_launches) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)batch), dim3(64), fixed_bytes + row_bytes, st, pa);
-        return;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)batch), dim3(64), lds, st, pa);
+        return ANET_OK;
       }
-      // stages: [0, split) for everybody, then the problems still running, each stage's workgroups handed their problems
-      // longest-expected first by what the stage before parked ([split, split2), [split2, ...) with ANET_LBFGS_SPLIT_EVALS2 set)
-      const int stops[3] = {split_evals, (split_evals2 > split_evals && max_evals > split_evals2) ? split_evals2 : 0, max_evals};
-      pa.cont = cont;
-      int prev = 0;
-      for (int stage = 0; stage < 3; ++stage) {
-        if (stops[stage] <= 0) continue;
-        const bool last = stage == 2;
-        pa.park = last ? 0 : 1;
-        pa.resume = prev > 0 ? 1 : 0;
-        pa.half_mark = (prev + stops[stage]) / 2;
-        pa.max_evals = stops[stage];
-        hipLaunchKernelGGL(kernel, dim3((unsigned)batch), dim3(64), fixed_bytes + row_bytes, st, pa);
-        if (last) break;
-        hipLaunchKernelGGL(k_lbfgs_resume_score, g256, b256, 0, st, L.is, cont, batch, ld, score);
-        if (launch_order_impl(ctx, batch, score, order2, bins, st, 0) != ANET_OK) {  // (cannot fail with these arguments; if it ever does:
-          order_failed = true;                                                       //  the error is the caller's return code)
-          return;
-        }
-        pa.order = order2;
-        prev = stops[stage];
-      }
+      // every problem through the first split_evals evaluations, parked; then the ones still running, longest-expected first
+      pa.cont = rt.cont;
+      pa.park = 1;
+      pa.half_mark = split_evals / 2;
+      pa.max_evals = split_evals;
+      hipLaunchKernelGGL(kernel, dim3((unsigned)batch), dim3(64), lds, st, pa);
+      return resume_parked(
+          ctx, batch, rt, st,
+          [&](int32_t *score) { hipLaunchKernelGGL(k_lbfgs_resume_score, g256, b256, 0, st, L.is, rt.cont, batch, ld, score); },
+          [&](const int32_t *order) {
+            pa.park = 0;
+            pa.resume = 1;
+            pa.half_mark = (split_evals + max_evals) / 2;
+            pa.max_evals = max_evals;
+            pa.order = order;
+            hipLaunchKernelGGL(kernel, dim3((unsigned)batch), dim3(64), lds, st, pa);
+            return ANET_OK;
+          });
     };
     const size_t lds_cap = 64 * 1024;
     bool launched = true;
     if (s == 3 && N <= 8 && anet::persist_lds_fixed_bytes<3, 8>() + row_bytes <= lds_cap)
-      launch(anet::k_lbfgs_minco_persistent<3, 8, 8>, anet::persist_lds_fixed_bytes<3, 8>());
+      rc = launch(anet::k_lbfgs_minco_persistent<3, 8, 8>, anet::persist_lds_fixed_bytes<3, 8>());
     else if (s == 3 && anet::persist_lds_fixed_bytes<3, 16>() + row_bytes <= lds_cap)
-      launch(anet::k_lbfgs_minco_persistent<3, 16, 8>, anet::persist_lds_fixed_bytes<3, 16>());
+      rc = launch(anet::k_lbfgs_minco_persistent<3, 16, 8>, anet::persist_lds_fixed_bytes<3, 16>());
     else if (s == 4 && N <= 8 && anet::persist_lds_fixed_bytes<4, 8>() + row_bytes <= lds_cap)
-      launch(anet::k_lbfgs_minco_persistent<4, 8, 8>, anet::persist_lds_fixed_bytes<4, 8>());
+      rc = launch(anet::k_lbfgs_minco_persistent<4, 8, 8>, anet::persist_lds_fixed_bytes<4, 8>());
     else if (s == 4 && anet::persist_lds_fixed_bytes<4, 16>() + row_bytes <= lds_cap)
-      launch(anet::k_lbfgs_minco_persistent<4, 16, 8>, anet::persist_lds_fixed_bytes<4, 16>());
+      rc = launch(anet::k_lbfgs_minco_persistent<4, 16, 8>, anet::persist_lds_fixed_bytes<4, 16>());
     else
       launched = false;
-    if (order_failed) return ANET_ERR_INVALID;
+    if (rc) return rc;  // (the counting sort between two launches cannot fail with these arguments; if it ever does: its error)
     if (launched) {
       ANET_HIP(ctx, hipGetLastError());
 #ifdef ANET_PERSIST_PROF
@@ -2176,12 +2059,14 @@ void anet_qp_default_settings(anet_qp_settings *s) {
   s->method = ANET_QP_METHOD_INTERIOR_POINT;
 }
 
+// the parked state of one interior-point problem (qp_ipm.h IpmArgs::cont): the iterate's ny doubles, then its scalars
+static int64_t qp_cont_doubles(int s, int n_pieces) { return (int64_t)3 * s * (n_pieces + 1) + anet::kIpmContScalars; }
+
 int64_t anet_qp_solve_workspace(int s, int n_pieces, int64_t batch, int res, int M) {
   const int64_t m = 3 * (6 + (int64_t)s * (n_pieces - 1)) + (int64_t)n_pieces * res * (M + 12);
-  // z, y, residuals; then (interior point, two-launch form) the parked state of every problem, its score and the launch order of
-  // the second part (int32 each) and the 4096 bins of the counting sort
-  const int64_t cont = (int64_t)3 * s * (n_pieces + 1) + anet::kIpmContScalars;
-  return 2 * m * batch + 2 * batch + cont * batch + batch + 4096 / 2 + 8;
+  // z, y, residuals; then (interior point, two-launch form) the tail the two launches hand the parked problems over in, and six
+  // doubles of slack
+  return 2 * m * batch + 2 * batch + ResumeTail::doubles(qp_cont_doubles(s, n_pieces), batch) + 6;
 }
 
 // Second part of a two-launch interior-point solve: what order its workgroups take the problems in.  Score of a parked problem,
@@ -2250,11 +2135,8 @@ static int qp_solve_dev_impl(anet_ctx *ctx, int s, int n_pieces, int64_t batch, 
     anet::IpmArgs ia{state, T, hpolys, work, work + mi * batch, coeffs, obj, status, iters,
                      residuals ? residuals : work + 2 * mi * batch, grad_T, grad_z, vjp_T, batch, n_pieces, res, M, max_vel,
                      max_acc, m34, tol, st_.max_iter < 200 ? st_.max_iter : 200, tol_plain > tol ? tol_plain : 0.0, 0.1 * tol, 0, launch_order, 0, 0, nullptr, nullptr};
-    static const int ipm_twist_min_pieces = [] {
-      const char *e = getenv("ANET_IPM_TWIST_MIN_PIECES");
-      return e ? atoi(e) : 2;
-    }();
-    ia.twist_min_pieces = ipm_twist_min_pieces;
+    const anet::Tuning &t = anet::tuning();
+    ia.twist_min_pieces = t.ipm_twist_min_pieces;
     hipStream_t sti = (hipStream_t)stream;
     if (launch_order) {
       hipLaunchKernelGGL(k_qp_mark_not_run, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, sti, batch, status, iters, obj);
@@ -2307,25 +2189,16 @@ static int qp_solve_dev_impl(anet_ctx *ctx, int s, int n_pieces, int64_t batch, 
       }
     } prof_dump{ctx, d_iprof, sti};
 #endif
-    // two workgroups per CU (registers bounded to 256) from this batch on, when two fit the LDS
-    static const int64_t two_per_cu_env = [] {
-      const char *e = getenv("ANET_IPM_TWO_PER_CU_MIN_BATCH");
-      return e ? (int64_t)atoll(e) : (int64_t)-1;
-    }();
-    // more than two rounds of one workgroup per CU (measured on 256 CUs): below that a batch lasts as long as its slowest problem
-    // and a problem alone on its CU is faster (512 problems are a draw -- 2.86 / 1.88 / 2.95 ms against 2.64 / 1.63 /
-    // 3.42 ms for 8 snap / 5 jerk / 5 snap pieces --, 768 problems gain 15-20 % from two per CU, 320 lose 15 %)
-    const int64_t ipm_two_per_cu_min_batch = two_per_cu_env >= 0 ? two_per_cu_env : 2 * (int64_t)ctx->cus + 1;
-    const bool two_per_cu = batch >= ipm_two_per_cu_min_batch && 2 * ldsb <= 160 * 1024;
+    // two workgroups per CU (registers bounded to 256) from this batch on, when two fit the LDS: more than two rounds of one
+    // workgroup per CU (measured on 256 CUs): below that a batch lasts as long as its slowest problem and a problem alone on its
+    // CU is faster (512 problems are a draw -- 2.86 / 1.88 / 2.95 ms against 2.64 / 1.63 / 3.42 ms for 8 snap / 5 jerk / 5 snap
+    // pieces --, 768 problems gain 15-20 % from two per CU, 320 lose 15 %)
+    const bool two_per_cu = batch >= t.ipm_two_per_cu_min_batch.at(ctx->cus) && 2 * ldsb <= 160 * 1024;
     // ... and THREE for jerk problems whose LDS allows it, from a batch on that fills them several times over (registers bounded
     // to 168: 464 B of scratch).  Measured (round 5, same box, 5 jerk pieces): 4096 problems 3.96-4.00 -> 3.77-3.85 ms; 3000:
     // 3.02-3.07 -> 3.21-3.25; 2048: 2.09-2.12 -> 2.42-2.43 (1024: 1.60 -> 1.91 in round 4) -- selected by batch like every other
     // shape here (ANET_IPM_THREE_PER_CU_MIN_BATCH overrides; 0 disables)
-    static const int64_t three_per_cu_env = [] {
-      const char *e = getenv("ANET_IPM_THREE_PER_CU_MIN_BATCH");
-      return e ? (int64_t)atoll(e) : (int64_t)-1;
-    }();
-    const int64_t ipm_three_per_cu_min_batch = three_per_cu_env >= 0 ? three_per_cu_env : per_cu(ctx, 4096);
+    const int64_t ipm_three_per_cu_min_batch = t.ipm_three_per_cu_min_batch.at(ctx->cus);
     const bool three_per_cu = s == 3 && two_per_cu && ipm_three_per_cu_min_batch > 0 && batch >= ipm_three_per_cu_min_batch &&
                               3 * ldsb <= 160 * 1024;
     auto launch_ipm = [&](auto kern) -> int {
@@ -2341,27 +2214,29 @@ static int qp_solve_dev_impl(anet_ctx *ctx, int s, int n_pieces, int64_t batch, 
     // Large batches in TWO launches (qp_ipm.h, IpmArgs::it_stop): the first takes every problem through the same number of Newton
     // steps -- no tail: all workgroups are equally long --, the second resumes the unfinished ones longest-expected first.  A batch
     // of 4096 in one launch ends 27 % above its balanced figure because its 30..50-step problems start whenever their turn comes.
-    static const int ipm_split_steps = [] { const char *e = getenv("ANET_IPM_SPLIT_STEPS"); return e ? atoi(e) : 4; }();
-    static const int64_t ipm_split_env = [] { const char *e = getenv("ANET_IPM_SPLIT_MIN_BATCH"); return e ? (int64_t)atoll(e) : (int64_t)-1; }();
-    const int64_t ipm_split_min_batch = ipm_split_env >= 0 ? ipm_split_env : per_cu(ctx, 576);  // (256 CUs: 520..560 problems lose 7-10 %, 600..1280 gain 10-19 %)
-    if (two_per_cu && ipm_split_steps > 0 && batch >= ipm_split_min_batch && !launch_order && ia.max_iter > ipm_split_steps) {
+    // (from 576 problems on 256 CUs: 520..560 problems lose 7-10 %, 600..1280 gain 10-19 %)
+    const int split_steps = t.ipm_split_steps;
+    if (two_per_cu && split_steps > 0 && batch >= t.ipm_split_min_batch.at(ctx->cus) && !launch_order && ia.max_iter > split_steps) {
       const int ny = 3 * s * (n_pieces + 1);
       const int64_t m_adm = 3 * (6 + (int64_t)s * (n_pieces - 1)) + mi;
-      double *cont = work + 2 * m_adm * batch + 2 * batch;
-      int32_t *score = (int32_t *)(cont + (int64_t)(ny + anet::kIpmContScalars) * batch);
-      int32_t *order2 = score + batch + (batch & 1);
-      int32_t *bins = order2 + batch + (batch & 1);
-      ia.cont = cont;
-      ia.it_stop = ipm_split_steps;
+      ResumeTail rt{qp_cont_doubles(s, n_pieces), batch};
+      rt.carve(work + 2 * m_adm * batch + 2 * batch);
+      ia.cont = rt.cont;
+      ia.it_stop = split_steps;
       rc_l = launch_throughput();
       if (rc_l != ANET_OK) return rc_l;
-      hipLaunchKernelGGL(k_qp_resume_score, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, sti, status, cont, batch, ny, tol, score);
-      rc_l = launch_order_impl(ctx, batch, score, order2, bins, sti, 0);
-      if (rc_l != ANET_OK) return rc_l;
-      ia.it_stop = 0;
-      ia.resume = 1;
-      ia.order = order2;
-      rc_l = launch_throughput();
+      rc_l = resume_parked(
+          ctx, batch, rt, sti,
+          [&](int32_t *score) {
+            hipLaunchKernelGGL(k_qp_resume_score, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, sti, status, rt.cont, batch, ny,
+                               tol, score);
+          },
+          [&](const int32_t *order) {
+            ia.it_stop = 0;
+            ia.resume = 1;
+            ia.order = order;
+            return launch_throughput();
+          });
       if (rc_l != ANET_OK) return rc_l;
       ANET_HIP(ctx, hipGetLastError());
       return ANET_OK;

@@ -5,7 +5,7 @@
 // The evaluation is the one of k_minco_solve / k_piece_grad / k_minco_propagate, re-mapped onto the 64 lanes of a
 // wave with every intermediate in LDS (10-13 KB per wave, plus the corridor rows):
 //   * of the block-tridiagonal solve only the factor's Schur-complement chain is walked node by node (one lane); the
-//     forward / backward sweeps, primal and adjoint, are parallel scans over (node, axis) rows of 16 lanes (chain_solve);
+//     forward / backward sweeps, primal and adjoint, are parallel scans over (node, axis) rows of 16 lanes (chain_solve_twisted);
 //     with the durations fixed the factor is computed once per problem;
 //   * everything per node or per piece (right-hand sides, coefficients, adjoint contributions, gradient terms) runs
 //     on lanes = (node | piece, axis);
@@ -73,7 +73,7 @@ struct PersistLds {
   double Kp[NB][m][m];       // coupling block Ko_k of piece k
   double Si[NB + 1][m][m];   // inverse Schur complements S_k^-1
   double H[NB][m][m];        // H_k = S_k^-1 Ko_k: y_k+1 = rhs_k+1 - H_k' y_k ;  x_k = z_k - H_k x_k+1
-  // X[axis][component][node], rows of XW doubles: the (node, axis) lanes and the 16-lane scan rows of chain_solve read one
+  // X[axis][component][node], rows of XW doubles: the (node, axis) lanes and the 16-lane scan rows of chain_solve_twisted read one
   // component of many nodes at a time -- node-minor keeps those on consecutive banks (node-major with 2 components per node put
   // 51 lanes on 16 same-parity double-banks: four-way); XW makes the axes start 16 double-banks apart where a small pad can
   static constexpr int xw_pad() {
@@ -92,11 +92,6 @@ struct PersistLds {
   double wl[NB + 1][3], gTp[NB][3], ep[NB][3];
   double mid[3][2][m];       // twisted sweeps: what the last node of either chain contributes to the middle node's right-hand side
 };
-// The block-tridiagonal system is eliminated from BOTH ends towards the middle node (1) or from node 0 to node N (0: the
-// one-ended walk, kept for A/B runs: tools/ab_build.sh "-DANET_PERSIST_TWISTED=0").
-#ifndef ANET_PERSIST_TWISTED
-#define ANET_PERSIST_TWISTED 1
-#endif
 
 template <int S, int NB>
 constexpr size_t persist_lds_fixed_bytes() { return (sizeof(PersistLds<S, NB>) + 15) / 16 * 16; }
@@ -509,13 +504,12 @@ __global__ void __launch_bounds__(64) k_lbfgs_mvie_resident(LbfgsArgs la, MvieAr
   }
 }
 
-// K v = rhs for the three axes at once, in place, given S_k^-1 and H_k (E2).
-// The two sweeps of the block LDL^T solve, y_k = rhs_k - H_{k-1}' y_{k-1} and x_k = z_k - H_k x_{k+1} (z_k = S_k^-1 y_k), are
-// affine recurrences with m x m matrices: instead of walking the nodes on three lanes they run as PARALLEL SCANS, one DPP row
-// of 16 lanes per axis (row 3 shadows axis 2), lane j = node j+1 forwards and node j backwards (the ends are folded into
-// their neighbours, so 17 nodes fit 16 lanes).  A round combines (M, v) -- "value = M * value(d nodes away) + v" -- with
-// the pair d lanes away: log2(N) rounds of row_shr / row_shl moves and m^3 + m^2 FMAs replace N dependent node steps
-// with their LDS round trips; rounding differs from the walk by a factor below two (tests/prototypes/scan_sweeps.py).
+// One round of the parallel scans that run the two sweeps of the block LDL^T solve (chain_solve_twisted).  The sweeps,
+// y_k = rhs_k - H_{k-1}' y_{k-1} and x_k = z_k - H_k x_{k+1} (z_k = S_k^-1 y_k), are affine recurrences with m x m matrices:
+// instead of walking the nodes on three lanes they run as PARALLEL SCANS, one DPP row of 16 lanes per axis (row 3 shadows
+// axis 2).  A round combines (M, v) -- "value = M * value(d nodes away) + v" -- with the pair d lanes away: log2 of the chain's
+// length in rounds of row_shr / row_shl moves and m^3 + m^2 FMAs replace dependent node steps with their LDS round trips;
+// rounding differs from the walk by a factor below two (tests/prototypes/scan_sweeps.py).
 template <int CTRL, int m>
 __device__ __forceinline__ void scan_round(double (&M)[m][m], double (&v)[m], const bool more) {
   double Mp[m][m], vp[m];
@@ -547,96 +541,8 @@ __device__ __forceinline__ void scan_round(double (&M)[m][m], double (&v)[m], co
   }
 }
 
-template <int S, int NB>
-__device__ __forceinline__ void chain_solve(PersistLds<S, NB> &Lm, double (&V)[3][S - 1][PersistLds<S, NB>::XW], const int N,
-                                            const int lane, const int, const int) {
-  constexpr int m = S - 1;
-  const int row = lane >> 4, j = lane & 15, ax = row < 3 ? row : 2;
-  const bool valid = j < N;                  // forward node j + 1 <= N, backward node j <= N - 1
-  const int jc = valid ? j : 0;
-  double Hj[m][m], M[m][m], v[m], y0[m], z0[m], zf[m];
-#pragma unroll
-  for (int a = 0; a < m; ++a) {
-    y0[a] = V[ax][a][0];
-    v[a] = valid ? V[ax][a][jc + 1] : 0.0;
-#pragma unroll
-    for (int b = 0; b < m; ++b) Hj[a][b] = valid ? Lm.H[jc][a][b] : 0.0;
-  }
-  // ---- forwards: y_{j+1} = rhs_{j+1} - H_j' y_j; lane 0 takes y_0 = rhs_0 in and starts the chain
-#pragma unroll
-  for (int a = 0; a < m; ++a)
-#pragma unroll
-    for (int b = 0; b < m; ++b) M[a][b] = -Hj[b][a];
-  if (j == 0) {
-#pragma unroll
-    for (int a = 0; a < m; ++a) {
-#pragma unroll
-      for (int b = 0; b < m; ++b) {
-        v[a] = __builtin_fma(M[a][b], y0[b], v[a]);
-      }
-    }
-#pragma unroll
-    for (int a = 0; a < m; ++a)
-#pragma unroll
-      for (int b = 0; b < m; ++b) M[a][b] = 0.0;
-  }
-  if (N > 1) scan_round<0x111, m>(M, v, N > 2);
-  if (N > 2) scan_round<0x112, m>(M, v, N > 4);
-  if (N > 4) scan_round<0x114, m>(M, v, N > 8);
-  if constexpr (NB > 8) {
-    if (N > 8) scan_round<0x118, m>(M, v, false);
-  }
-  // ---- z = S^-1 y on the lane of its node; z_j arrives from the left neighbour, z_0 is computed by lane 0
-#pragma unroll
-  for (int a = 0; a < m; ++a) {
-    double acc = 0.0, acc0 = 0.0;
-#pragma unroll
-    for (int b = 0; b < m; ++b) {
-      acc = __builtin_fma(Lm.Si[jc + 1][a][b], v[b], acc);
-      acc0 = __builtin_fma(Lm.Si[0][a][b], y0[b], acc0);
-    }
-    zf[a] = valid ? acc : 0.0;
-    z0[a] = acc0;
-  }
-#pragma unroll
-  for (int a = 0; a < m; ++a) {
-    const double zl = dpp_f64<0x111>(zf[a]);
-    v[a] = (j == 0) ? z0[a] : zl;
-    if (!valid) v[a] = 0.0;
-  }
-  // ---- backwards: x_j = z_j - H_j x_{j+1}; lane N-1 takes x_N = z_N in and starts the chain
-#pragma unroll
-  for (int a = 0; a < m; ++a)
-#pragma unroll
-    for (int b = 0; b < m; ++b) M[a][b] = -Hj[a][b];
-  if (j == N - 1) {
-#pragma unroll
-    for (int a = 0; a < m; ++a)
-#pragma unroll
-      for (int b = 0; b < m; ++b) v[a] = __builtin_fma(M[a][b], zf[b], v[a]);
-#pragma unroll
-    for (int a = 0; a < m; ++a)
-#pragma unroll
-      for (int b = 0; b < m; ++b) M[a][b] = 0.0;
-  }
-  if (N > 1) scan_round<0x101, m>(M, v, N > 2);
-  if (N > 2) scan_round<0x102, m>(M, v, N > 4);
-  if (N > 4) scan_round<0x104, m>(M, v, N > 8);
-  if constexpr (NB > 8) {
-    if (N > 8) scan_round<0x108, m>(M, v, false);
-  }
-  if (valid && row < 3) {
-#pragma unroll
-    for (int a = 0; a < m; ++a) V[ax][a][j] = v[a];
-    if (j == N - 1) {
-#pragma unroll
-      for (int a = 0; a < m; ++a) V[ax][a][N] = zf[a];
-    }
-  }
-  __syncthreads();
-}
-
-// The same solve with the TWISTED factor of E2: nodes 0 .. pm-1 were eliminated upwards (S_k), nodes N .. pm+1 downwards (R_k),
+// K v = rhs for the three axes at once, in place, with the TWISTED factor of E2 (the block-tridiagonal system eliminated
+// from both ends towards the middle node): nodes 0 .. pm-1 were eliminated upwards (S_k), nodes N .. pm+1 downwards (R_k),
 // the middle node pm = N / 2 last.  Lm.Si[k] holds S_k^-1 (k < pm), R_k^-1 (k > pm) or the inverse of the middle block;
 // Lm.H[i] (piece i, between nodes i and i+1) holds S_i^-1 Ko_i for i < pm and R_{i+1}^-1 Ko_i' for i >= pm -- in either chain
 // "the inverse of the node FARTHER from the middle times the coupling towards the nearer one".  A row of 16 lanes per axis
@@ -832,10 +738,9 @@ __device__ __forceinline__ void persist_eval(PersistLds<S, NB> &Lm, const double
   //      This is the only part that is sequential in earnest: per node two (three) reciprocals in a row.  Its inputs
   //      come from LDS a few nodes at a time into alternating register buffers (a load-then-use per node is an LDS
   //      round trip of dead time per node); what the sweeps need of it leaves as S_k^-1 and H_k = S_k^-1 Ko_k, so
-  //      the sweeps are bare m x m recurrences (chain_solve) and the products with S_k^-1 run on lanes = (node, axis).
+  //      the sweeps are bare m x m recurrences (chain_solve_twisted) and the products with S_k^-1 run on lanes = (node, axis).
   // The system depends on the durations only: with the durations fixed (waypoints-only optimisation) it is factorised
   // by the first evaluation and S_k^-1, H_k stay in LDS for the rest of the run.
-#if ANET_PERSIST_TWISTED
   // TWISTED: lane 0 walks nodes 0 .. pm-1 upwards, lane 1 walks nodes N .. pm+1 downwards -- the same instructions on
   // two lanes, so half the chain costs nothing extra -- and lane 0 finishes with the middle node pm = N / 2, whose block takes a
   // Schur term from either side.  The downward chain is the upward one with every coupling block transposed.  (Measured by
@@ -1040,164 +945,6 @@ __device__ __forceinline__ void persist_eval(PersistLds<S, NB> &Lm, const double
   }
   if constexpr (m > 2) __syncthreads();
   chain_solve_twisted<S, NB>(Lm, Lm.X, N, lane);
-#else
-  if (lane == 0 && refactor) {
-    constexpr int CH = (m <= 2) ? 4 : 2;
-    double Dk[m][m];
-#pragma unroll
-    for (int j = 0; j < m; ++j)
-#pragma unroll
-      for (int l = 0; l < m; ++l) Dk[j][l] = 0.0;
-    auto load = [&](int k0, double (&BA)[CH][m][m], double (&BK)[CH][m][m]) {
-#pragma unroll
-      for (int u = 0; u < CH; ++u) {
-        const int kk = (k0 + u <= N) ? k0 + u : N, kp = (kk < N) ? kk : (N > 0 ? N - 1 : 0);
-#pragma unroll
-        for (int j = 0; j < m; ++j)
-#pragma unroll
-          for (int l = 0; l < m; ++l) {
-            if (l <= j) BA[u][j][l] = Lm.Ad[kk][j][l];
-            BK[u][j][l] = Lm.Kp[kp][j][l];
-          }
-      }
-    };
-    auto step = [&](const int k, const double (&Ak)[m][m], const double (&Kk)[m][m]) {
-#pragma unroll
-      for (int j = 0; j < m; ++j)
-#pragma unroll
-        for (int l = 0; l <= j; ++l) Dk[j][l] += Ak[j][l];
-      if constexpr (m == 2) {
-        // 2 x 2: the inverse by its adjugate (same rounding as the LDL^T route -- tests/prototypes/scan_sweeps.py -- one
-        // reciprocal instead of two on the chain), S_k^-1 and H_k = S_k^-1 Ko_k stored right away
-        const double r = fast_rcp(__builtin_fma(Dk[0][0], Dk[1][1], -Dk[1][0] * Dk[1][0]));
-        const double s00 = Dk[1][1] * r, s11 = Dk[0][0] * r, s10 = -Dk[1][0] * r;
-        Lm.Si[k][0][0] = s00; Lm.Si[k][0][1] = s10; Lm.Si[k][1][0] = s10; Lm.Si[k][1][1] = s11;
-        if (k < N) {
-          double W[2][2];
-#pragma unroll
-          for (int b = 0; b < 2; ++b) {
-            W[0][b] = __builtin_fma(s00, Kk[0][b], s10 * Kk[1][b]);
-            W[1][b] = __builtin_fma(s10, Kk[0][b], s11 * Kk[1][b]);
-            Lm.H[k][0][b] = W[0][b];
-            Lm.H[k][1][b] = W[1][b];
-          }
-#pragma unroll
-          for (int aa = 0; aa < 2; ++aa)
-#pragma unroll
-            for (int bb = 0; bb <= aa; ++bb) Dk[aa][bb] = -__builtin_fma(Kk[0][aa], W[0][bb], Kk[1][aa] * W[1][bb]);
-        }
-        return;
-      }
-      double Lk[NLA] = {}, dd[m], dik[m];
-#pragma unroll
-      for (int j = 0; j < m; ++j) {
-        double dj = Dk[j][j];
-        double ld_[m];
-#pragma unroll
-        for (int q = 0; q < j; ++q) {
-          ld_[q] = Lk[BlkOps<S>::li(j, q)] * dd[q];
-          dj = __builtin_fma(-ld_[q], Lk[BlkOps<S>::li(j, q)], dj);
-        }
-        dd[j] = dj;
-        dik[j] = fast_rcp(dj);
-#pragma unroll
-        for (int i = j + 1; i < m; ++i) {
-          double v = Dk[i][j];
-#pragma unroll
-          for (int q = 0; q < j; ++q) v = __builtin_fma(-Lk[BlkOps<S>::li(i, q)], ld_[q], v);
-          Lk[BlkOps<S>::li(i, j)] = v * dik[j];
-        }
-      }
-      if (k < N) {  // Schur complement seed for node k+1: the chain continues with it
-        double Y[m][m], Z[m][m];
-#pragma unroll
-        for (int l = 0; l < m; ++l) {
-          double col[m];
-#pragma unroll
-          for (int j = 0; j < m; ++j) col[j] = Kk[j][l];
-          BlkOps<S>::solve_L(Lk, col);
-#pragma unroll
-          for (int j = 0; j < m; ++j) {
-            Y[j][l] = col[j];
-            Z[j][l] = col[j] * dik[j];
-          }
-        }
-#pragma unroll
-        for (int aa = 0; aa < m; ++aa)
-#pragma unroll
-          for (int bb = 0; bb <= aa; ++bb) {
-            double acc = 0.0;
-#pragma unroll
-            for (int j = 0; j < m; ++j) acc = __builtin_fma(-Y[j][aa], Z[j][bb], acc);
-            Dk[aa][bb] = acc;
-          }
-      }
-      // the factor of the node, for the lanes that turn it into S_k^-1 and H_k below: [1/d | L] in the slot of S_k^-1
-      double *slot = &Lm.Si[k][0][0];
-#pragma unroll
-      for (int j = 0; j < m; ++j) slot[j] = dik[j];
-#pragma unroll
-      for (int q = 0; q < BlkOps<S>::nl; ++q) slot[m + q] = Lk[q];
-    };
-    double A1[CH][m][m], K1[CH][m][m], A2[CH][m][m], K2[CH][m][m];
-    load(0, A1, K1);
-#pragma unroll 1
-    for (int k0 = 0; k0 <= N; k0 += 2 * CH) {
-      load(k0 + CH, A2, K2);
-#pragma unroll
-      for (int u = 0; u < CH; ++u)
-        if (k0 + u <= N) step(k0 + u, A1[u], K1[u]);
-      load(k0 + 2 * CH, A1, K1);
-#pragma unroll
-      for (int u = 0; u < CH; ++u)
-        if (k0 + CH + u <= N) step(k0 + CH + u, A2[u], K2[u]);
-    }
-  }
-  __syncthreads();
-  // S_k^-1 = L^-T D^-1 L^-1 and H_k = S_k^-1 Ko_k are off the chain: every node on its own lane (3 x 3 blocks)
-  if (m > 2 && refactor && lane <= N) {
-    const int k = lane;
-    double Lk[NLA] = {}, dik[m];
-    const double *slot = &Lm.Si[k][0][0];
-#pragma unroll
-    for (int j = 0; j < m; ++j) dik[j] = slot[j];
-#pragma unroll
-    for (int q = 0; q < BlkOps<S>::nl; ++q) Lk[q] = slot[m + q];
-    if (k < N) {
-#pragma unroll
-      for (int l = 0; l < m; ++l) {
-        double col[m];
-#pragma unroll
-        for (int j = 0; j < m; ++j) col[j] = Lm.Kp[k][j][l];
-        BlkOps<S>::solve_L(Lk, col);
-#pragma unroll
-        for (int j = 0; j < m; ++j) col[j] *= dik[j];
-        BlkOps<S>::solve_LT(Lk, col);
-#pragma unroll
-        for (int j = 0; j < m; ++j) Lm.H[k][j][l] = col[j];
-      }
-    }
-    double Sk[m][m];
-#pragma unroll
-    for (int cc = 0; cc < m; ++cc) {
-      double col[m];
-#pragma unroll
-      for (int j = 0; j < m; ++j) col[j] = (j == cc) ? 1.0 : 0.0;
-      BlkOps<S>::solve_L(Lk, col);
-#pragma unroll
-      for (int j = 0; j < m; ++j) col[j] *= dik[j];
-      BlkOps<S>::solve_LT(Lk, col);
-#pragma unroll
-      for (int j = 0; j < m; ++j) Sk[j][cc] = col[j];
-    }
-#pragma unroll
-    for (int j = 0; j < m; ++j)
-#pragma unroll
-      for (int cc = 0; cc < m; ++cc) Lm.Si[k][j][cc] = Sk[j][cc];
-  }
-  if constexpr (m > 2) __syncthreads();
-  chain_solve<S, NB>(Lm, Lm.X, N, lane, na, ax);
-#endif
 
   PERSIST_TICK(2);
   PERSIST_PHASE();
@@ -1504,11 +1251,7 @@ __device__ __forceinline__ void persist_eval(PersistLds<S, NB> &Lm, const double
     }
   }
   __syncthreads();
-#if ANET_PERSIST_TWISTED
   chain_solve_twisted<S, NB>(Lm, Lm.X, N, lane);
-#else
-  chain_solve<S, NB>(Lm, Lm.X, N, lane, na, ax);
-#endif
 
   PERSIST_TICK(6);
   PERSIST_PHASE();

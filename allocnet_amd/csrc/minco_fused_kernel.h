@@ -27,6 +27,7 @@
 #pragma once
 #include "minco_kernels.h"
 #include "piece_grad_mx.h"
+#include "tuning.h"
 
 namespace anet {
 
@@ -933,6 +934,13 @@ __global__ void __launch_bounds__(MX ? 512 : 256, 1) k_minco_cost_grad_fused(Fus
     if (a.cost && live1 && ax1 == 0) a.cost[bb1] = e_tot + a.pp.rho * tsum + csum;
     ANET_FP(13);
   }
+}
+
+// Does the one-launch evaluation of (order s, c boundary derivatives, N pieces, res samples per piece) run its phase 2 on the matrix
+// instructions (MX)?  The exact shapes at kMxRes samples, unless ANET_FUSED_MX=0.  (launch_fused_t further needs groups of at least
+// 16 (trajectory, piece) pairs; cost_grad_in_one_launch sizes the rounds of groups by it.)
+inline bool fused_phase2_mx(int s, int c, int n_pieces, int res) {
+  return tuning().fused_mx && res == kMxRes && c == 3 && ((s == 4 && n_pieces == 8) || (s == 3 && n_pieces == 16));
 }
 
 // false: no instantiation for this shape (the caller takes the three-launch path)

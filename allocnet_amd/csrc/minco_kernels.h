@@ -1050,4 +1050,31 @@ __global__ void __launch_bounds__(kSolveBlock) k_minco_propagate_axis(PropArgs a
 // the small-batch adjoint (lane = (trajectory, axis)), in the same translation unit as k_piece_grad and for the same reason
 void launch_propagate_axis(int s, const PropArgs &a, dim3 grid, dim3 block, hipStream_t st);
 
+// The compile-time shape of a MINCO kernel instantiation: pieces NB (an upper bound unless EXACT), boundary derivatives NPC + 1
+template <int NB_, bool EXACT_ = false, int NPC_ = -1>
+struct MincoShape {
+  static constexpr int NB = NB_, NPC = NPC_;
+  static constexpr bool EXACT = EXACT_;
+};
+
+// The one shape ladder of the solve / sample / propagate kernels of order S: f(MincoShape<...>{}) with the fully specialised
+// instantiation for the shapes the benchmarks and the planner use -- 8-piece snap, 16-piece jerk, five pieces (the planner's
+// own: learning_planner.hpp:179), all with c = 3 (PVA ends), and 8-piece snap with c = 4 unless C4 is false --, else the generic
+// one for N <= 4 / 8 / 16.
+template <int S, bool C4 = true, class F>
+void with_minco_shape(int N, int c, F &&f) {
+  if constexpr (S == 4) {
+    if (N == 8 && c == 3) return f(MincoShape<8, true, 2>{});
+    if constexpr (C4)
+      if (N == 8 && c == 4) return f(MincoShape<8, true, 3>{});
+    if (N == 5 && c == 3) return f(MincoShape<5, true, 2>{});
+  } else if constexpr (S == 3) {
+    if (N == 16 && c == 3) return f(MincoShape<16, true, 2>{});
+    if (N == 5 && c == 3) return f(MincoShape<5, true, 2>{});
+  }
+  if (N <= 4) f(MincoShape<4>{});
+  else if (N <= 8) f(MincoShape<8>{});
+  else f(MincoShape<16>{});
+}
+
 }  // namespace anet

@@ -3,11 +3,11 @@
 // -mllvm -amdgpu-sched-strategy=max-ilp (allocnet_amd/build.py; why: the comment at launch_piece_grad's declaration).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "minco_kernels.h"
 #include "minco_fused_kernel.h"
 #include "piece_grad_mx.h"
+#include "tuning.h"
 
 namespace anet {
 
@@ -15,8 +15,7 @@ void launch_piece_grad(int s, int shape, dim3 grid, dim3 block, hipStream_t st, 
   if (shape == 3) {  // large batches, res = 20, orders 3 / 4: the table contractions on the matrix instructions (piece_grad_mx.h)
     // (ANET_PGMX_DYNLDS: bytes of unused dynamic LDS per workgroup -- an occupancy probe for tools/, never set otherwise)
     static const int dyn = [] {
-      const char *e = getenv("ANET_PGMX_DYNLDS");
-      const int v = e ? atoi(e) : 0;
+      const int v = tuning().pgmx_dynlds;
       if (v > 0) {
         (void)hipFuncSetAttribute((const void *)k_piece_grad_mx<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, v);
         (void)hipFuncSetAttribute((const void *)k_piece_grad_mx<4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, v);
@@ -56,17 +55,10 @@ void launch_piece_grad(int s, int shape, dim3 grid, dim3 block, hipStream_t st, 
 
 template <int S>
 static void launch_propagate_axis_t(const PropArgs &a, dim3 g3, dim3 block, hipStream_t st) {
-  if constexpr (S == 4) {
-    if (a.N == 8 && a.c == 3) { hipLaunchKernelGGL((k_minco_propagate_axis<4, 8, true, 2>), g3, block, 0, st, a); return; }
-    if (a.N == 8 && a.c == 4) { hipLaunchKernelGGL((k_minco_propagate_axis<4, 8, true, 3>), g3, block, 0, st, a); return; }
-    if (a.N == 5 && a.c == 3) { hipLaunchKernelGGL((k_minco_propagate_axis<4, 5, true, 2>), g3, block, 0, st, a); return; }
-  } else if constexpr (S == 3) {
-    if (a.N == 16 && a.c == 3) { hipLaunchKernelGGL((k_minco_propagate_axis<3, 16, true, 2>), g3, block, 0, st, a); return; }
-    if (a.N == 5 && a.c == 3) { hipLaunchKernelGGL((k_minco_propagate_axis<3, 5, true, 2>), g3, block, 0, st, a); return; }
-  }
-  if (a.N <= 4) hipLaunchKernelGGL((k_minco_propagate_axis<S, 4>), g3, block, 0, st, a);
-  else if (a.N <= 8) hipLaunchKernelGGL((k_minco_propagate_axis<S, 8>), g3, block, 0, st, a);
-  else hipLaunchKernelGGL((k_minco_propagate_axis<S, 16>), g3, block, 0, st, a);
+  with_minco_shape<S>(a.N, a.c, [&](auto sh) {
+    using Sh = decltype(sh);
+    hipLaunchKernelGGL((k_minco_propagate_axis<S, Sh::NB, Sh::EXACT, Sh::NPC>), g3, block, 0, st, a);
+  });
 }
 
 void launch_propagate_axis(int s, const PropArgs &a, dim3 grid, dim3 block, hipStream_t st) {
@@ -89,12 +81,11 @@ static void launch_fused_t(const FusedArgs &a_in, const double *tab, hipStream_t
   while (G > 1 && (a.B + G / 2 - 1) / (G / 2) <= cus && (G / 2) * NB >= 8) G /= 2;
   a.G = G;
   const dim3 grid((unsigned)((a.B + G - 1) / G));
-  // Full groups of the exact shapes at 20 samples per piece: phase 2 on the matrix instructions (minco_fused_kernel.h, MX).
-  // ANET_FUSED_MX=0 keeps the vector sample loop (A-B runs).
-  if constexpr (NEXACT && NPC >= 0 && FusedShape<NB>::G * NB == 128) {
-    static const int mx = [] { const char *e = getenv("ANET_FUSED_MX"); return e ? atoi(e) : 1; }();
-    // (groups of at least two column sets of 16 pairs: G NB >= 32; a wave per column set, four waves at least)
-    if (mx && G * NB >= 16 && a.pp.res == kMxRes) {
+  // The exact shapes (full groups: GM NB = 128) at kMxRes samples per piece: phase 2 on the matrix instructions
+  // (minco_fused_kernel.h, MX) in groups of at least one column set of 16 pairs; a wave per column set, four waves at least
+  if constexpr (NEXACT) {
+    static_assert(NPC >= 0 && GM * NB == 128, "the MX form is built for full groups of the exact shapes");
+    if (fused_phase2_mx(S, a.c, a.N, a.pp.res) && G * NB >= 16) {
       const int waves = G * NB / 16 < 4 ? 4 : G * NB / 16;
       hipLaunchKernelGGL((k_minco_cost_grad_fused<S, NB, NEXACT, NPC, true>), grid, dim3(64 * waves), 0, st, a, tab);
       return;

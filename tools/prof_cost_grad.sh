@@ -1,6 +1,6 @@
 #!/bin/bash
 # Per-kernel times of three cost + gradient evaluations at B = 131072 (tools/run_cost_grad.py) from the kernel trace:
-#   gpurun --timeout 600 -- 'bash tools/prof_cost_grad.sh [tag]'     (env such as ANET_PIECE_LIST_MIN_BATCH is passed on)
+#   bash tools/prof_cost_grad.sh [tag]     (on the GPU machine, from the repository root; env such as ANET_PG_MX is passed on)
 TAG=${1:-a}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_cg_$TAG

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel device time of one cost + gradient evaluation (bench.cost_grad_kernel_split) and the fused evaluation's time
 (bench.timed_reps) for given shapes:  python tools/split_cost_grad.py 4,3,8,4096 [...]   (order, boundary count, pieces, batch).
-Launch shapes are chosen by the library (override: ANET_PIECE_SHAPE, ANET_PIECE_SW_MAX_PAIRS, ANET_AXIS_MAX_BATCH); ANET_RES = samples per piece (default 20)."""
+Launch shapes are chosen by the library (overrides: ANET_PIECE_SW_MAX_PAIRS, ANET_AXIS_MAX_BATCH); ANET_RES = samples per piece (default 20)."""
 import os, sys
 import numpy as np
 ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
