@@ -19,4 +19,7 @@ from . import firi as _firi_mod  # noqa: F401
 from .firi import (firi, firi_dev, firi_params, convex_cover, polytope_depth, find_interior, overlap,  # noqa: F401
                    overlap_pt, short_cut, pack_model_inputs, to_planner_form)
 
+from . import voxel_map  # noqa: F401
+from .voxel_map import VoxelMap, gather_boxes_dev  # noqa: F401
+
 __version__ = "0.1.0"

@@ -95,6 +95,16 @@ PROTOTYPES = {
     "anet_firi_var_dev": (c_int, [c_void_p, c_int64, c_int, c_int, c_int] + [c_void_p] * 13),
     "anet_firi_workspace": (c_int64, [c_int64, c_int, c_int]),
     "anet_firi_dev": (c_int, [c_void_p, c_int64, c_int, c_int, c_int] + [c_void_p] * 12),
+    "anet_voxel_set_occupied_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
+    "anet_voxel_set_occupied_ids_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "anet_voxel_workspace": (c_int64, [c_void_p]),
+    "anet_voxel_dilate_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "anet_voxel_surface_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "anet_voxel_surf_points_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "anet_voxel_query_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "anet_voxel_gather_workspace": (c_int64, [c_int64, c_int64]),
+    "anet_voxel_gather_boxes_dev": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                                            c_void_p, c_void_p]),
     "anet_comm_unique_id": (c_int, [c_void_p, c_void_p]),
     "anet_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "anet_comm_allgather_costs_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
@@ -145,6 +155,11 @@ class FiriParams(ctypes.Structure):
     """struct anet_firi_params (defaults of firi::firi / maxVolInsEllipsoid)."""
     _fields_ = [("iterations", ctypes.c_int32), ("epsilon", c_double), ("smooth_eps", c_double),
                 ("penalty_wt", c_double), ("mvie_max_evals", ctypes.c_int32)]
+
+
+class VoxelGrid(ctypes.Structure):
+    """struct anet_voxel_grid: voxel counts per axis, the map's origin and the voxel edge length."""
+    _fields_ = [("size", ctypes.c_int32 * 3), ("origin", c_double * 3), ("scale", c_double)]
 
 
 class QpDims(ctypes.Structure):

@@ -7,6 +7,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <cmath>
 #include <string>
 #include <vector>
 #include <new>
@@ -28,6 +29,7 @@
 #include "qp_admm.h"
 #include "qp_ipm.h"
 #include "layout_kernels.h"
+#include "voxel_kernels.h"
 #include "tuning.h"
 
 // ------------------------------------------------------------------------------------------
@@ -2545,6 +2547,164 @@ int anet_traj_max_rate(anet_ctx *ctx, int s, int n_pieces, int64_t batch, const 
   rc = anet_traj_max_rate_dev(ctx, s, n_pieces, batch, st.ld, d_co, d_T, which, d_r, ctx->stream);
   if (rc) return rc;
   return st.download(d_r, n_pieces, rate);
+}
+
+// ---- voxel map (csrc/voxel_kernels.h) -----------------------------------------------------------
+static bool vox_grid_of(const anet_voxel_grid *g, anet::VoxGrid *out) {
+#pragma clang fp contract(off)
+  if (!g || g->size[0] < 1 || g->size[1] < 1 || g->size[2] < 1) return false;
+  if ((int64_t)g->size[0] * g->size[1] * g->size[2] >= ((int64_t)1 << 31)) return false;
+  if (!(g->scale > 0.0) || !std::isfinite(g->scale)) return false;
+  for (int c = 0; c < 3; ++c)
+    if (!std::isfinite(g->origin[c])) return false;
+  out->sx = g->size[0]; out->sy = g->size[1]; out->sz = g->size[2];
+  out->scale = g->scale;
+  const int step[3] = {1, g->size[0], g->size[0] * g->size[1]};
+  for (int c = 0; c < 3; ++c) {  // voxel_map.hpp's constructor: oc = o + 0.5 scale, stepScale = (1 / step) scale
+    out->o[c] = g->origin[c];
+    out->oc[c] = g->origin[c] + 0.5 * g->scale;
+    out->ss[c] = (1.0 / (double)step[c]) * g->scale;
+  }
+  return true;
+}
+static int64_t vox_count(const anet::VoxGrid &g) { return (int64_t)g.sx * g.sy * g.sz; }
+static int64_t comp_chunks(int64_t n) { return (n + anet::kCompChunk - 1) / anet::kCompChunk; }
+// workspace: two fronts of a byte per voxel, then the per-chunk counts of the compaction
+static int64_t vox_front_bytes(int64_t n) { return round_up(2 * n, 256); }
+
+int anet_voxel_set_occupied_dev(anet_ctx *ctx, const anet_voxel_grid *grid, uint8_t *voxels, const void *records, int64_t n,
+                                int64_t stride, int f64, void *stream) {
+  ANET_ON_DEVICE(ctx);
+  anet::VoxGrid g;
+  if (!vox_grid_of(grid, &g)) return fail(ctx, ANET_ERR_INVALID, "anet_voxel_set_occupied_dev: bad grid (size >= 1, voxels < 2^31, scale > 0)");
+  const int64_t esz = f64 ? 8 : 4;
+  if (n < 0 || (f64 != 0 && f64 != 1) || stride < 3 * esz || stride % esz)
+    return fail(ctx, ANET_ERR_INVALID, "anet_voxel_set_occupied_dev: n >= 0, f64 in {0, 1}, stride >= 3 elements and a multiple of one");
+  if (n == 0) return ANET_OK;
+  if (!voxels || !records || (uintptr_t)records % esz) return fail(ctx, ANET_ERR_INVALID, "anet_voxel_set_occupied_dev: NULL or misaligned pointer");
+  hipLaunchKernelGGL(anet::k_voxel_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, voxels,
+                     (const uint8_t *)records, n, stride, f64);
+  ANET_HIP(ctx, hipGetLastError());
+  return ANET_OK;
+}
+
+int anet_voxel_set_occupied_ids_dev(anet_ctx *ctx, const anet_voxel_grid *grid, uint8_t *voxels, const int32_t *ids, int64_t n,
+                                    void *stream) {
+  ANET_ON_DEVICE(ctx);
+  anet::VoxGrid g;
+  if (!vox_grid_of(grid, &g)) return fail(ctx, ANET_ERR_INVALID, "anet_voxel_set_occupied_ids_dev: bad grid (size >= 1, voxels < 2^31, scale > 0)");
+  if (n < 0) return fail(ctx, ANET_ERR_INVALID, "anet_voxel_set_occupied_ids_dev: n < 0");
+  if (n == 0) return ANET_OK;
+  if (!voxels || !ids) return fail(ctx, ANET_ERR_INVALID, "anet_voxel_set_occupied_ids_dev: NULL pointer");
+  hipLaunchKernelGGL(anet::k_voxel_scatter_ids, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, voxels, ids, n);
+  ANET_HIP(ctx, hipGetLastError());
+  return ANET_OK;
+}
+
+int64_t anet_voxel_workspace(const anet_voxel_grid *grid) {
+  anet::VoxGrid g;
+  if (!vox_grid_of(grid, &g)) return -1;
+  return vox_front_bytes(vox_count(g)) + 4 * comp_chunks(vox_count(g));
+}
+
+int anet_voxel_dilate_dev(anet_ctx *ctx, const anet_voxel_grid *grid, uint8_t *voxels, int r, void *work, void *stream) {
+  ANET_ON_DEVICE(ctx);
+  anet::VoxGrid g;
+  if (!vox_grid_of(grid, &g)) return fail(ctx, ANET_ERR_INVALID, "anet_voxel_dilate_dev: bad grid (size >= 1, voxels < 2^31, scale > 0)");
+  if (r <= 0) return ANET_OK;  // voxel_map.hpp: no-op, the surface stays what it was
+  if (!voxels || !work) return fail(ctx, ANET_ERR_INVALID, "anet_voxel_dilate_dev: NULL pointer");
+  const int64_t n = vox_count(g);
+  uint8_t *front[2] = {(uint8_t *)work, (uint8_t *)work + n};
+  const int64_t tx = (g.sx + anet::kDilTX - 1) / anet::kDilTX, ty = (g.sy + anet::kDilTY - 1) / anet::kDilTY,
+                tz = (g.sz + anet::kDilTZ - 1) / anet::kDilTZ;
+  hipStream_t st = (hipStream_t)stream;
+  // round k writes front[(r - k) & 1], so the last round's front is front[0] whatever r is
+  for (int k = 1; k <= r; ++k) {
+    hipLaunchKernelGGL(anet::k_voxel_dilate_round, dim3((unsigned)(tx * ty * tz)), dim3(anet::kDilTX, anet::kDilTY), 0, st, g,
+                       voxels, front[(r - k + 1) & 1], front[(r - k) & 1], k == 1 ? 1 : 0, tx, ty);
+    ANET_HIP(ctx, hipGetLastError());
+  }
+  return ANET_OK;
+}
+
+int anet_voxel_surface_dev(anet_ctx *ctx, const anet_voxel_grid *grid, void *work, int64_t cap, int32_t *ids, int32_t *count,
+                           void *stream) {
+  ANET_ON_DEVICE(ctx);
+  anet::VoxGrid g;
+  if (!vox_grid_of(grid, &g)) return fail(ctx, ANET_ERR_INVALID, "anet_voxel_surface_dev: bad grid (size >= 1, voxels < 2^31, scale > 0)");
+  if (cap < 0 || !work || !count || (cap > 0 && !ids)) return fail(ctx, ANET_ERR_INVALID, "anet_voxel_surface_dev: cap >= 0, NULL pointer");
+  const int64_t n = vox_count(g), nc = comp_chunks(n);
+  int32_t *counts = (int32_t *)((uint8_t *)work + vox_front_bytes(n));
+  anet::FrontPred p{(const uint8_t *)work, ids};
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(anet::k_compact_count<anet::FrontPred>, dim3((unsigned)nc), dim3(anet::kCompThreads), 0, st, p, n, nc, counts);
+  ANET_HIP(ctx, hipGetLastError());
+  hipLaunchKernelGGL(anet::k_compact_scan, dim3(1), dim3(anet::kCompThreads), 0, st, counts, nc, count);
+  ANET_HIP(ctx, hipGetLastError());
+  if (cap > 0) {
+    hipLaunchKernelGGL(anet::k_compact_write<anet::FrontPred>, dim3((unsigned)nc), dim3(anet::kCompThreads), 0, st, p, n, nc, counts, cap);
+    ANET_HIP(ctx, hipGetLastError());
+  }
+  return ANET_OK;
+}
+
+int anet_voxel_surf_points_dev(anet_ctx *ctx, const anet_voxel_grid *grid, const int32_t *ids, int64_t n, double *out,
+                               void *stream) {
+  ANET_ON_DEVICE(ctx);
+  anet::VoxGrid g;
+  if (!vox_grid_of(grid, &g)) return fail(ctx, ANET_ERR_INVALID, "anet_voxel_surf_points_dev: bad grid (size >= 1, voxels < 2^31, scale > 0)");
+  if (n < 0) return fail(ctx, ANET_ERR_INVALID, "anet_voxel_surf_points_dev: n < 0");
+  if (n == 0) return ANET_OK;
+  if (!ids || !out) return fail(ctx, ANET_ERR_INVALID, "anet_voxel_surf_points_dev: NULL pointer");
+  hipLaunchKernelGGL(anet::k_voxel_surf_points, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, ids, n, out);
+  ANET_HIP(ctx, hipGetLastError());
+  return ANET_OK;
+}
+
+int anet_voxel_query_dev(anet_ctx *ctx, const anet_voxel_grid *grid, const uint8_t *voxels, const double *pos, int64_t n,
+                         uint8_t *out, void *stream) {
+  ANET_ON_DEVICE(ctx);
+  anet::VoxGrid g;
+  if (!vox_grid_of(grid, &g)) return fail(ctx, ANET_ERR_INVALID, "anet_voxel_query_dev: bad grid (size >= 1, voxels < 2^31, scale > 0)");
+  if (n < 0) return fail(ctx, ANET_ERR_INVALID, "anet_voxel_query_dev: n < 0");
+  if (n == 0) return ANET_OK;
+  if (!voxels || !pos || !out) return fail(ctx, ANET_ERR_INVALID, "anet_voxel_query_dev: NULL pointer");
+  hipLaunchKernelGGL(anet::k_voxel_query, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, voxels, pos, n, out);
+  ANET_HIP(ctx, hipGetLastError());
+  return ANET_OK;
+}
+
+int64_t anet_voxel_gather_workspace(int64_t n_boxes, int64_t n_points) {
+  if (n_boxes < 0 || n_boxes > 65535 || n_points < 0 || n_points >= ((int64_t)1 << 31)) return -1;
+  return 4 * (n_boxes * comp_chunks(n_points) + 1);
+}
+
+int anet_voxel_gather_boxes_dev(anet_ctx *ctx, int64_t n_boxes, const double *bd, const double *points, int64_t n_points,
+                                int64_t max_points, void *work, double *out, int32_t *n_out, void *stream) {
+  ANET_ON_DEVICE(ctx);
+  if (n_boxes < 0 || n_boxes > 65535 || n_points < 0 || n_points >= ((int64_t)1 << 31) || max_points < 0)
+    return fail(ctx, ANET_ERR_INVALID, "anet_voxel_gather_boxes_dev: 0 <= n_boxes <= 65535, 0 <= n_points < 2^31, max_points >= 0");
+  if (n_boxes == 0) return ANET_OK;
+  if (!bd || !work || !n_out || (n_points > 0 && !points) || (max_points > 0 && !out))
+    return fail(ctx, ANET_ERR_INVALID, "anet_voxel_gather_boxes_dev: NULL pointer");
+  hipStream_t st = (hipStream_t)stream;
+  if (n_points == 0) {
+    ANET_HIP(ctx, hipMemsetAsync(n_out, 0, sizeof(int32_t) * n_boxes, st));
+    return ANET_OK;
+  }
+  const int64_t nc = comp_chunks(n_points);
+  int32_t *counts = (int32_t *)work;
+  anet::BoxPred p{bd, points, out};
+  const dim3 grid((unsigned)nc, (unsigned)n_boxes);
+  hipLaunchKernelGGL(anet::k_compact_count<anet::BoxPred>, grid, dim3(anet::kCompThreads), 0, st, p, n_points, nc, counts);
+  ANET_HIP(ctx, hipGetLastError());
+  hipLaunchKernelGGL(anet::k_compact_scan, dim3((unsigned)n_boxes), dim3(anet::kCompThreads), 0, st, counts, nc, n_out);
+  ANET_HIP(ctx, hipGetLastError());
+  if (max_points > 0) {
+    hipLaunchKernelGGL(anet::k_compact_write<anet::BoxPred>, grid, dim3(anet::kCompThreads), 0, st, p, n_points, nc, counts, max_points);
+    ANET_HIP(ctx, hipGetLastError());
+  }
+  return ANET_OK;
 }
 
 }  // extern "C"

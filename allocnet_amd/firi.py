@@ -52,10 +52,11 @@ def firi(bd, pc, a, b, n_points=None, max_rows=64, params=None, ctx=None, iterat
     return dict(hpoly=hp, n_rows=nh, ok=ok, ellipsoid=ell)
 
 
-def firi_dev(bd, pc, n_points, a, b, max_rows=64, params=None, stream=None, ctx=None):
+def firi_dev(bd, pc, n_points, a, b, max_rows=64, params=None, stream=None, ctx=None, iterations=None):
     """anet_firi_dev: the same with torch CUDA tensors in and out (float64 bd (B,Mb,4), pc (B,Np,3), a, b (B,3);
     int32 n_points (B,)).  Nothing leaves the device; asynchronous on `stream` (default: torch's current stream).
-    Returns dict(hpoly (B,max_rows,4), n_rows, ok, ellipsoid) of device tensors."""
+    iterations: optional int32 CUDA tensor (B,) of pass counts per corridor (anet_firi_var_dev, which clamps them to
+    [1, params.iterations]).  Returns dict(hpoly (B,max_rows,4), n_rows, ok, ellipsoid) of device tensors."""
     import torch
     ctx = ctx or default_context()
     B, Mb, _ = bd.shape
@@ -65,6 +66,9 @@ def firi_dev(bd, pc, n_points, a, b, max_rows=64, params=None, stream=None, ctx=
             raise ValueError("float64 contiguous CUDA tensors expected")
     if not (n_points.is_cuda and n_points.dtype == torch.int32 and n_points.is_contiguous() and n_points.shape == (B,)):
         raise ValueError("n_points: int32 contiguous CUDA tensor of shape (B,)")
+    if iterations is not None and not (iterations.is_cuda and iterations.dtype == torch.int32 and iterations.is_contiguous()
+                                       and iterations.shape == (B,)):
+        raise ValueError("iterations: int32 contiguous CUDA tensor of shape (B,)")
     dev = bd.device
     hp = torch.empty((B, max_rows, 4), device=dev, dtype=torch.float64)
     nh = torch.empty(B, device=dev, dtype=torch.int32); ok = torch.empty(B, device=dev, dtype=torch.int32)
@@ -72,12 +76,13 @@ def firi_dev(bd, pc, n_points, a, b, max_rows=64, params=None, stream=None, ctx=
     work = torch.empty(int(ctx.lib.anet_firi_workspace(B, Np, int(max_rows))), device=dev, dtype=torch.float64)
     st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
     pp = ctypes.cast(ctypes.pointer(params), ctypes.c_void_p) if params is not None else None
-    ctx.check(ctx.lib.anet_firi_dev(ctx.handle, B, Mb, Np, int(max_rows), ctypes.c_void_p(bd.data_ptr()),
-                                    ctypes.c_void_p(pc.data_ptr()) if Np else None,
-                                    ctypes.c_void_p(n_points.data_ptr()) if Np else None, ctypes.c_void_p(a.data_ptr()),
-                                    ctypes.c_void_p(b.data_ptr()), pp, ctypes.c_void_p(work.data_ptr()),
-                                    ctypes.c_void_p(hp.data_ptr()), ctypes.c_void_p(nh.data_ptr()),
-                                    ctypes.c_void_p(ok.data_ptr()), ctypes.c_void_p(ell.data_ptr()), ctypes.c_void_p(st)))
+    its = ctypes.c_void_p(iterations.data_ptr()) if iterations is not None else None
+    ctx.check(ctx.lib.anet_firi_var_dev(ctx.handle, B, Mb, Np, int(max_rows), ctypes.c_void_p(bd.data_ptr()),
+                                        ctypes.c_void_p(pc.data_ptr()) if Np else None,
+                                        ctypes.c_void_p(n_points.data_ptr()) if Np else None, ctypes.c_void_p(a.data_ptr()),
+                                        ctypes.c_void_p(b.data_ptr()), its, pp, ctypes.c_void_p(work.data_ptr()),
+                                        ctypes.c_void_p(hp.data_ptr()), ctypes.c_void_p(nh.data_ptr()),
+                                        ctypes.c_void_p(ok.data_ptr()), ctypes.c_void_p(ell.data_ptr()), ctypes.c_void_p(st)))
     return dict(hpoly=hp, n_rows=nh, ok=ok, ellipsoid=ell, _work=work)
 
 
@@ -116,9 +121,16 @@ def convex_cover(path, points, low_corner, high_corner, progress, rng_range, eps
     polytope per step inside the box [segment -/+ range] clipped to the map, plus a gap polytope where
     consecutive ones barely overlap at the shared point.  The segments are independent, so all FIRI calls
     of a path run as ONE batch (then one more batch for the gap polytopes).  Returns a list of (n_i,4)
-    arrays in raw form."""
+    arrays in raw form.
+
+    points: (n, 3) obstacle points, or a VoxelMap: then each segment's points are selected from the map's surface on the
+    device (anet_voxel_gather_boxes_dev) and go to the device FIRI without a round trip through the host; the result is
+    bitwise that of convex_cover(path, vm.getSurf(), ...)."""
+    from .voxel_map import VoxelMap
+    vmap = points if isinstance(points, VoxelMap) else None
     path = [np.asarray(p, dtype=np.float64) for p in path]
-    points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    if vmap is None:
+        points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
     lo_c = np.asarray(low_corner, dtype=np.float64); hi_c = np.asarray(high_corner, dtype=np.float64)
     segs = []
     bq = path[0]
@@ -142,20 +154,25 @@ def convex_cover(path, points, low_corner, high_corner, progress, rng_range, eps
         for ax in range(3):
             bd[k, 2 * ax, ax] = 1.0; bd[k, 2 * ax, 3] = -hi[ax]
             bd[k, 2 * ax + 1, ax] = -1.0; bd[k, 2 * ax + 1, 3] = lo[ax]
-        inside = ((points @ bd[k, :, :3].T + bd[k, :, 3]).max(axis=1) < 0.0) if len(points) else np.zeros(0, dtype=bool)
-        sel.append(points[inside])
-    Np = max(1, max(len(s) for s in sel))
-    pc = np.zeros((B, Np, 3)); npts = np.zeros(B, dtype=np.int32)
-    for k, s in enumerate(sel):
-        pc[k, :len(s)] = s; npts[k] = len(s)
+        if vmap is None:
+            inside = ((points @ bd[k, :, :3].T + bd[k, :, 3]).max(axis=1) < 0.0) if len(points) else np.zeros(0, dtype=bool)
+            sel.append(points[inside])
     A = np.array([s[0] for s in segs]); Bv = np.array([s[1] for s in segs])
     # One batch: the B segments with the default pass count and, speculatively, the B - 1 gap polytopes of
     # sfc_gen.hpp:171-179 (firi::firi(bd, pc, a, a, gap, 1): ONE pass, so only a planes kernel each) -- whether a gap
     # polytope is needed depends on the segments' results, but computing all of them costs less than a second call.
     jn = list(range(1, B))
-    allr = firi(np.concatenate([bd, bd[jn]]), np.concatenate([pc, pc[jn]]), np.concatenate([A, A[jn]]),
-                np.concatenate([Bv, A[jn]]), n_points=np.concatenate([npts, npts[jn]]), max_rows=max_rows,
-                iterations=np.r_[np.full(B, firi_params().iterations, dtype=np.int32), np.ones(B - 1, dtype=np.int32)], ctx=ctx)
+    its = np.r_[np.full(B, firi_params().iterations, dtype=np.int32), np.ones(B - 1, dtype=np.int32)]
+    if vmap is None:
+        Np = max(1, max(len(s) for s in sel))
+        pc = np.zeros((B, Np, 3)); npts = np.zeros(B, dtype=np.int32)
+        for k, s in enumerate(sel):
+            pc[k, :len(s)] = s; npts[k] = len(s)
+        allr = firi(np.concatenate([bd, bd[jn]]), np.concatenate([pc, pc[jn]]), np.concatenate([A, A[jn]]),
+                    np.concatenate([Bv, A[jn]]), n_points=np.concatenate([npts, npts[jn]]), max_rows=max_rows,
+                    iterations=its, ctx=ctx)
+    else:
+        allr = _firi_on_map(vmap, bd, jn, A, Bv, its, max_rows, ctx or vmap.ctx)
     polys = [allr["hpoly"][k, :allr["n_rows"][k]] for k in range(B)]
     gaps = {}
     for k in range(1, B):
@@ -169,6 +186,22 @@ def convex_cover(path, points, low_corner, high_corner, progress, rng_range, eps
             out.append(gaps[k])
         out.append(polys[k])
     return out
+
+
+def _firi_on_map(vmap, bd, jn, A, Bv, its, max_rows, ctx):
+    """convex_cover's FIRI batch with the obstacle points selected on the device from the map's surface: the same
+    boxes, points, pass counts and padding as the host path, so the same kernels see the same inputs."""
+    import torch
+    dev = vmap.device
+    pc, npts = vmap.gather_boxes(bd)
+    jt = torch.tensor(jn, dtype=torch.long, device=dev)
+
+    def up(x, dt=torch.float64):
+        return torch.from_numpy(np.ascontiguousarray(x)).to(device=dev, dtype=dt)
+    r = firi_dev(up(np.concatenate([bd, bd[jn]])), torch.cat([pc, pc[jt]]).contiguous(),
+                 up(np.concatenate([npts, npts[jn]]), torch.int32), up(np.concatenate([A, A[jn]])),
+                 up(np.concatenate([Bv, A[jn]])), max_rows=max_rows, ctx=ctx, iterations=up(its, torch.int32))
+    return dict(hpoly=r["hpoly"].cpu().numpy(), n_rows=r["n_rows"].cpu().numpy())
 
 
 def polytope_depth(hpolys, normalise=True, ctx=None):

@@ -87,3 +87,56 @@ def firi_pack(cases):
     for i, c in enumerate(cases):
         pc[i, :len(c[1])] = c[1]; npts[i] = len(c[1])
     return bd, pc, npts, a, b
+
+
+def forest_cloud(rng, n_points=1_000_000, size=(40.0, 40.0, 5.0), origin=(-20.0, -20.0, 0.0), n_trees=120, n_boxes=20,
+                 nan_frac=0.01, clear_route=None, clearance=1.0, point_step=16):
+    """A synthetic scan of a forest: vertical cylinders (trees, radius U(0.15, 0.5), full height) and boxes sampled on
+    their surfaces, as PointCloud2 float32 records of `point_step` bytes (x, y, z, then padding) -- an (n, point_step / 4)
+    float32 array.  About nan_frac of the records are NaN (dropped returns).  clear_route: an optional polyline (m, 3)
+    no obstacle comes within `clearance` of, so a corridor along it exists."""
+    o = np.asarray(origin, dtype=np.float64); ext = np.asarray(size, dtype=np.float64)
+
+    def clear(c, r):
+        if clear_route is None:
+            return True
+        P = np.asarray(clear_route, dtype=np.float64)[:, :2]
+        for a, b in zip(P[:-1], P[1:]):
+            d = b - a
+            t = np.clip((c - a) @ d / max(d @ d, 1e-12), 0.0, 1.0)
+            if np.linalg.norm(c - (a + t * d)) < r + clearance:
+                return False
+        return True
+    trees, boxes = [], []
+    while len(trees) < n_trees:
+        c = o[:2] + rng.uniform(0.0, 1.0, 2) * ext[:2]; r = rng.uniform(0.15, 0.5)
+        if clear(c, r):
+            trees.append((c, r))
+    while len(boxes) < n_boxes:
+        c = o[:2] + rng.uniform(0.0, 1.0, 2) * ext[:2]; h = rng.uniform(0.3, 1.5, 3)
+        if clear(c, np.linalg.norm(h[:2])):
+            boxes.append((c, h))
+    n_tree_pts = int(n_points * 0.8); n_box_pts = n_points - n_tree_pts
+    k = rng.integers(0, len(trees), n_tree_pts)
+    cen = np.array([t[0] for t in trees])[k]; rad = np.array([t[1] for t in trees])[k]
+    th = rng.uniform(0.0, 2.0 * np.pi, n_tree_pts)
+    tree_pts = np.stack([cen[:, 0] + rad * np.cos(th), cen[:, 1] + rad * np.sin(th),
+                         o[2] + rng.uniform(0.0, 1.0, n_tree_pts) * ext[2]], axis=1)
+    k = rng.integers(0, len(boxes), n_box_pts)
+    cen = np.array([b[0] for b in boxes])[k]; half = np.array([b[1] for b in boxes])[k]
+    u = rng.uniform(-1.0, 1.0, (n_box_pts, 3))
+    face = rng.integers(0, 3, n_box_pts)
+    u[np.arange(n_box_pts), face] = np.sign(u[np.arange(n_box_pts), face])   # onto a face
+    box_pts = np.stack([cen[:, 0], cen[:, 1], o[2] + half[:, 2]], axis=1) + u * half
+    pts = np.concatenate([tree_pts, box_pts])[rng.permutation(n_points)]
+    rec = np.zeros((n_points, point_step // 4), dtype=np.float32)
+    rec[:, :3] = pts
+    rec[rng.uniform(size=n_points) < nan_frac, :3] = np.nan
+    return rec
+
+
+def forest_route(origin=(-20.0, -20.0, 0.0), size=(40.0, 40.0, 5.0), z=1.5):
+    """A five-leg polyline across the forest_cloud map (its clear_route)."""
+    o = np.asarray(origin, dtype=np.float64); e = np.asarray(size, dtype=np.float64)
+    f = np.array([[0.08, 0.08], [0.3, 0.22], [0.45, 0.5], [0.62, 0.55], [0.78, 0.8], [0.92, 0.92]])
+    return np.concatenate([o[:2] + f * e[:2], np.full((len(f), 1), o[2] + z)], axis=1)

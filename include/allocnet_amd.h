@@ -666,6 +666,47 @@ int anet_firi_var_dev(anet_ctx *ctx, int64_t batch, int n_bd, int max_points, in
                       const int32_t *iterations, const anet_firi_params *params, double *work, double *hpoly,
                       int32_t *n_rows, int32_t *ok, double *ellipsoid, void *stream);
 
+/* ---- voxel map: cloud occupancy, dilation, surface and the corridor's point selection ---------------- */
+/* voxel_map::VoxelMap (gcopter/voxel_map.hpp, voxel_dilater.hpp) on a device byte grid: voxel (x, y, z) at
+ * x + size[0] * (y + size[1] * z), values 0 Unoccupied, 1 Occupied, 2 Dilated; size[0] * size[1] * size[2] < 2^31.
+ * Byte-identical voxels and bit-identical surface coordinates; the surface is in ASCENDING voxel index order (the
+ * reference's is in breadth-first discovery order: the same set).  Device pointers, asynchronous on `stream`.      */
+typedef struct anet_voxel_grid {
+  int32_t size[3];
+  double origin[3];
+  double scale;
+} anet_voxel_grid;
+/* setOccupied for n records `stride` bytes apart, each starting with three float32 (f64 = 0, a PointCloud2 with
+ * point_step = stride) or float64 (f64 = 1) coordinates: records with a non-finite coordinate are skipped
+ * (mapCallBack), the index is ((pos - o) / scale) truncated toward zero, out-of-range points are dropped.           */
+int anet_voxel_set_occupied_dev(anet_ctx *ctx, const anet_voxel_grid *grid, uint8_t *voxels, const void *records, int64_t n,
+                                int64_t stride, int f64, void *stream);
+/* setOccupied(Eigen::Vector3i id) for n index triples ids [n][3] (x, y, z): in-bounds voxels are set to 1, the rest dropped */
+int anet_voxel_set_occupied_ids_dev(anet_ctx *ctx, const anet_voxel_grid *grid, uint8_t *voxels, const int32_t *ids, int64_t n,
+                                    void *stream);
+/* bytes of device workspace of anet_voxel_dilate_dev / anet_voxel_surface_dev (-1: bad grid) */
+int64_t anet_voxel_workspace(const anet_voxel_grid *grid);
+/* dilate(r): r synchronous 26-neighbour frontier rounds (round 1 grows from the voxels == 1, each later round from the
+ * voxels the previous one added, only into voxels == 0; grown voxels become 2).  r <= 0 does nothing.  The last round's
+ * front stays in `work` for anet_voxel_surface_dev until the next dilate on that workspace.                          */
+int anet_voxel_dilate_dev(anet_ctx *ctx, const anet_voxel_grid *grid, uint8_t *voxels, int r, void *work, void *stream);
+/* the surface (the voxels the last round of the last dilate added) as ascending linear ids: min(count, cap) written to
+ * ids, the true count to *count (device int32).                                                                    */
+int anet_voxel_surface_dev(anet_ctx *ctx, const anet_voxel_grid *grid, void *work, int64_t cap, int32_t *ids, int32_t *count,
+                           void *stream);
+/* getSurf: out [n][3] = id * stepScale + oc in the reference's offset form, the product and the sum each rounded.   */
+int anet_voxel_surf_points_dev(anet_ctx *ctx, const anet_voxel_grid *grid, const int32_t *ids, int64_t n, double *out,
+                               void *stream);
+/* query: out[i] = 1 when position i (pos [n][3]) is outside the map or in a voxel != 0, else 0                      */
+int anet_voxel_query_dev(anet_ctx *ctx, const anet_voxel_grid *grid, const uint8_t *voxels, const double *pos, int64_t n,
+                         uint8_t *out, void *stream);
+/* convexCover's per-segment selection: for box k (bd [n_boxes][6][4], the layout of anet_firi's bd), the points p of
+ * points [n_points][3] with max_r(bd[k][r][:3] . p + bd[k][r][3]) < 0, in their order, into out [n_boxes][max_points][3]
+ * (rows past the count untouched); n_out[k] = the true count, which may exceed max_points.                           */
+int64_t anet_voxel_gather_workspace(int64_t n_boxes, int64_t n_points);
+int anet_voxel_gather_boxes_dev(anet_ctx *ctx, int64_t n_boxes, const double *bd, const double *points, int64_t n_points,
+                                int64_t max_points, void *work, double *out, int32_t *n_out, void *stream);
+
 /* ---- multi-GPU: all-gather of the per-trajectory costs over RCCL / xGMI --------------------------- */
 /* Trajectories are independent, so a batch shards contiguously across GPUs (one process and one
  * context per GPU) with no collective inside a solve; the only exchange the path has is this

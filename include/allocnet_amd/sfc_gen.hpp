@@ -17,15 +17,15 @@
 
 namespace sfc_gen {
 
-template <typename V3, typename Poly>
-inline void convexCover(const std::vector<V3> &path, const std::vector<V3> &points, const V3 &lowCorner,
-                        const V3 &highCorner, const double &progress, const double &range, std::vector<Poly> &hpolys,
-                        const double eps = 1.0e-6) {
-  hpolys.clear();
+namespace detail {
+
+// the walk (sfc_gen.hpp:135-148): segments (a, b) of at most `progress`, and their bounding boxes clipped to the map
+// (sfc_gen.hpp:150-159) as bd [S][6][4]
+template <typename V3>
+inline int cover_segments(const std::vector<V3> &path, const V3 &lowCorner, const V3 &highCorner, const double &progress,
+                          const double &range, std::vector<double> &A, std::vector<double> &Bv, std::vector<double> &bd) {
   const int n = (int)path.size();
-  if (n < 2) return;
-  // the walk (sfc_gen.hpp:135-148): segments (a, b) of at most `progress`
-  std::vector<double> A, Bv;
+  if (n < 2) return 0;
   double b[3] = {path[0](0), path[0](1), path[0](2)};
   for (int i = 1; i < n;) {
     const double a[3] = {b[0], b[1], b[2]};
@@ -41,10 +41,7 @@ inline void convexCover(const std::vector<V3> &path, const std::vector<V3> &poin
     Bv.insert(Bv.end(), b, b + 3);
   }
   const int S = (int)(A.size() / 3);
-  // bounding boxes and the obstacle points inside each (sfc_gen.hpp:150-165)
-  std::vector<double> bd((size_t)S * 24, 0.0);
-  std::vector<std::vector<double>> sel(S);
-  size_t Np = 1;
+  bd.assign((size_t)S * 24, 0.0);
   for (int k = 0; k < S; ++k) {
     double *q = bd.data() + (size_t)k * 24;
     for (int ax = 0; ax < 3; ++ax) {
@@ -54,15 +51,14 @@ inline void convexCover(const std::vector<V3> &path, const std::vector<V3> &poin
       q[(2 * ax + 1) * 4 + ax] = -1.0;
       q[(2 * ax + 1) * 4 + 3] = +std::fmax(std::fmin(a, bb) - range, lowCorner(ax));
     }
-    for (const V3 &p : points) {
-      bool inside = true;
-      for (int r = 0; r < 6 && inside; ++r)
-        inside = q[r * 4] * p(0) + q[r * 4 + 1] * p(1) + q[r * 4 + 2] * p(2) + q[r * 4 + 3] < 0.0;
-      if (inside)
-        for (int c = 0; c < 3; ++c) sel[k].push_back(p(c));
-    }
-    if (sel[k].size() / 3 > Np) Np = sel[k].size() / 3;
   }
+  return S;
+}
+
+// from the segments' obstacle points sel[k] (x y z triples) on: the FIRI batch, the gap polytopes and the output list
+template <typename Poly>
+inline void cover_finish(int S, const std::vector<double> &A, const std::vector<double> &Bv, const std::vector<double> &bd,
+                         const std::vector<std::vector<double>> &sel, size_t Np, const double eps, std::vector<Poly> &hpolys) {
   std::vector<double> pc((size_t)S * Np * 3, 0.0);
   std::vector<int32_t> npts(S);
   for (int k = 0; k < S; ++k) {
@@ -132,6 +128,33 @@ inline void convexCover(const std::vector<V3> &path, const std::vector<V3> &poin
     if (g < need.size() && need[g] == k) emit(gapp[g++]);
     emit(mainp[k]);
   }
+}
+
+}  // namespace detail
+
+template <typename V3, typename Poly>
+inline void convexCover(const std::vector<V3> &path, const std::vector<V3> &points, const V3 &lowCorner,
+                        const V3 &highCorner, const double &progress, const double &range, std::vector<Poly> &hpolys,
+                        const double eps = 1.0e-6) {
+  hpolys.clear();
+  std::vector<double> A, Bv, bd;
+  const int S = detail::cover_segments(path, lowCorner, highCorner, progress, range, A, Bv, bd);
+  if (S == 0) return;
+  // the obstacle points inside each box (sfc_gen.hpp:160-165)
+  std::vector<std::vector<double>> sel(S);
+  size_t Np = 1;
+  for (int k = 0; k < S; ++k) {
+    const double *q = bd.data() + (size_t)k * 24;
+    for (const V3 &p : points) {
+      bool inside = true;
+      for (int r = 0; r < 6 && inside; ++r)
+        inside = q[r * 4] * p(0) + q[r * 4 + 1] * p(1) + q[r * 4 + 2] * p(2) + q[r * 4 + 3] < 0.0;
+      if (inside)
+        for (int c = 0; c < 3; ++c) sel[k].push_back(p(c));
+    }
+    if (sel[k].size() / 3 > Np) Np = sel[k].size() / 3;
+  }
+  detail::cover_finish(S, A, Bv, bd, sel, Np, eps, hpolys);
 }
 
 template <typename Poly>
