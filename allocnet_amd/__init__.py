@@ -21,5 +21,7 @@ from .firi import (firi, firi_dev, firi_params, convex_cover, polytope_depth, fi
 
 from . import voxel_map  # noqa: F401
 from .voxel_map import VoxelMap, gather_boxes_dev  # noqa: F401
+from . import path_search  # noqa: F401
+from .path_search import plan_path, plan_paths, PATH_EXACT, PATH_APPROXIMATE, PATH_INVALID_START  # noqa: F401
 
 __version__ = "0.1.0"

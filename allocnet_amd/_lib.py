@@ -105,6 +105,12 @@ PROTOTYPES = {
     "anet_voxel_gather_workspace": (c_int64, [c_int64, c_int64]),
     "anet_voxel_gather_boxes_dev": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                                             c_void_p, c_void_p]),
+    "anet_voxel_path_workspace": (c_int64, [c_void_p, c_int64]),
+    "anet_voxel_path_field_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                          c_void_p]),
+    "anet_voxel_path_field_ptr": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "anet_voxel_path_extract_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                            c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "anet_comm_unique_id": (c_int, [c_void_p, c_void_p]),
     "anet_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "anet_comm_allgather_costs_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

@@ -189,6 +189,13 @@ class VoxelMap:
         """((pos - o) / scale) truncated toward zero."""
         return ((np.asarray(pos, dtype=np.float64) - self._o) / self._scale).astype(np.int32)
 
+    # ---- planPath's field --------------------------------------------------------------------------
+    def path_field_dev(self, starts, lb=None, hb=None):
+        """Cost-to-come fields of the starts (B, 3) over the free voxels of [lb, hb] (default the map's box): ((B, n_voxels)
+        uint32 CUDA tensor view, valid until the map's next search; rounds).  See path_search.plan_path."""
+        from .path_search import path_field_dev
+        return path_field_dev(self, starts, lb, hb)
+
     # ---- convexCover's per-segment selection --------------------------------------------------------
     def gather_boxes(self, bd, points=None):
         """For each box k of bd (K, 6, 4) (rows h . [p; 1] < 0 inside), the surface points inside it, in surface order,

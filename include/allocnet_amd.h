@@ -707,6 +707,41 @@ int64_t anet_voxel_gather_workspace(int64_t n_boxes, int64_t n_points);
 int anet_voxel_gather_boxes_dev(anet_ctx *ctx, int64_t n_boxes, const double *bd, const double *points, int64_t n_points,
                                 int64_t max_points, void *work, double *out, int32_t *n_out, void *stream);
 
+/* ---- front-end route on the voxel map: sfc_gen::planPath ----------------------------------------------------------------
+ * A collision-free polyline from s to g and its length, by a shortest-path field on the grid, a walk back along it and a
+ * line-of-sight shortcut; exact and deterministic (no time budget).  box = {lb[3], hb[3]} (host array), the planner's
+ * [getOrigin(), getCorner()] by default.
+ *   free voxel  byte 0 and its centre posI2D(id) = id * scale + (origin + 0.5 scale) inside [lb, hb]; a position is free
+ *               when query(pos) == 0 and its voxel is free.
+ *   graph       26 neighbours, weights 10 / 14 / 17 (face / edge / corner); a move by d is an edge only when every voxel
+ *               cur + e, e_i in {0, d_i}, is free (no corner cutting).  The field is uint32 cost-to-come, UINT32_MAX
+ *               unreached; grids with 17 * voxels >= 2^32 - 1 are refused (ANET_ERR_UNSUPPORTED).
+ *   target      g when g is free and reached (EXACT), else the centre of the reached voxel nearest to g, least squared
+ *               distance in double, ties to the lowest id (APPROXIMATE).  A start that is not free: INVALID_START, cost
+ *               INFINITY, no points.
+ *   walk        from the target voxel, the first neighbour in the order dz, dy, dx in {-1, 0, 1} with d[n] + w == d[cur]
+ *               and an edge; waypoints s, the centres of the walk's voxels after the start's, the target (g when EXACT);
+ *               s and g in one voxel give [s, g].
+ *   shortcut    greedy from W_0: the next waypoint is the LARGEST k whose segment is visible (a 3-D DDA visits only free
+ *               voxels; where crossings of several axes tie, the whole block of that step is checked).
+ *   cost        the sum of the final segments' lengths, in path order.                                                   */
+enum { ANET_PATH_EXACT = 0, ANET_PATH_APPROXIMATE = 1, ANET_PATH_INVALID_START = 2 };
+/* bytes of device workspace for n_problems searches on `grid` (fields, walks, activity words); -1: bad or too large grid */
+int64_t anet_voxel_path_workspace(const anet_voxel_grid *grid, int64_t n_problems);
+/* the cost-to-come fields of the starts [n_problems][3] (device) into `work`, by rounds of tile relaxation; *rounds (host)
+ * = the rounds that had an active tile.  SYNCHRONISES `stream` (it reads a device word every 8 rounds to stop).         */
+int anet_voxel_path_field_dev(anet_ctx *ctx, const anet_voxel_grid *grid, const uint8_t *voxels, const double box[6],
+                              const double *starts, int64_t n_problems, void *work, int32_t *rounds, void *stream);
+/* problem b's field [n_voxels] uint32 inside `work` (no device access)                                                 */
+int anet_voxel_path_field_ptr(const anet_voxel_grid *grid, void *work, int64_t b, uint32_t **field);
+/* target, walk, shortcut and cost for (starts[b], goals[b]) on the fields of the last anet_voxel_path_field_dev on `work`
+ * (same grid, voxels, box and starts): paths [n_problems][max_points][3] get min(count, max_points) points, n_points[b]
+ * the true count (call again with a larger max_points when it exceeds it; max_points = 0 writes no points), cost[b],
+ * status[b] (ANET_PATH_*, or -1 when the fields do not belong to these starts).  Device outputs, asynchronous.          */
+int anet_voxel_path_extract_dev(anet_ctx *ctx, const anet_voxel_grid *grid, const uint8_t *voxels, const double box[6],
+                                const double *starts, const double *goals, int64_t n_problems, void *work, int64_t max_points,
+                                double *paths, int32_t *n_points, double *cost, int32_t *status, void *stream);
+
 /* ---- multi-GPU: all-gather of the per-trajectory costs over RCCL / xGMI --------------------------- */
 /* Trajectories are independent, so a batch shards contiguously across GPUs (one process and one
  * context per GPU) with no collective inside a solve; the only exchange the path has is this
