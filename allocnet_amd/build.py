@@ -8,13 +8,15 @@ to the GPU box with the repo snapshot.
 import os
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC_DIR = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "liballocnet_amd.so")
-SOURCES = ["allocnet_amd.hip"]
+# the C ABI, one translation unit per domain (csrc/api_internal.h lists them)
+SOURCES = ["api_context.hip", "api_solve.hip", "api_cost_grad.hip", "api_lbfgs.hip", "api_qp.hip", "api_voxel.hip"]
 # translation units with flags of their own: (source, extra flags)
 UNITS = [("piece_grad_unit.hip", ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
          ("qp_ipm_fuse_unit.hip", ["-mllvm", "-amdgpu-sched-strategy=max-ilp"])]
@@ -65,34 +67,29 @@ def build(force=False, verbose=False):
     import tempfile
     os.makedirs(LIB_DIR, exist_ok=True)
     extra = os.environ.get("ANET_BUILD_FLAGS", "").split()      # e.g. -DANET_PERSIST_PROF (tools/ only)
-    # the units compile while the main source does (-mllvm flags are per invocation), then everything is linked
+    # every unit compiles in a process of its own (-mllvm flags are per invocation), then everything is linked: at most MAX_JOBS
+    # compiles at once when it is set, never more than 16
     cflags = [f for f in FLAGS if f not in ("-shared", "-ldl")] + probe_flags(MFMA_VGPR_FORM)
-    jobs, objs = [], []
     tmp = tempfile.TemporaryDirectory(prefix="anet_build_")     # the objects do not stay in the tree
-    OBJ_DIR = tmp.name
-    for src, uflags in UNITS:
-        obj = os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".o")
+    cmds, objs = [], []
+    for src, uflags in [(s, []) for s in SOURCES] + UNITS:
+        obj = os.path.join(tmp.name, os.path.splitext(src)[0] + ".o")
         objs.append(obj)
-        ucmd = [HIPCC] + cflags + uflags + extra + ["-c", os.path.join(SRC_DIR, src), "-o", obj]
+        cmds.append([HIPCC] + cflags + uflags + extra + ["-c", os.path.join(SRC_DIR, src), "-o", obj])
         if verbose:
-            print(" ".join(ucmd), flush=True)
-        jobs.append((ucmd, subprocess.Popen(ucmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
-    main_objs = []
-    for src in SOURCES:
-        obj = os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".o")
-        main_objs.append(obj)
-        mcmd = [HIPCC] + cflags + extra + ["-c", os.path.join(SRC_DIR, src), "-o", obj]
-        if verbose:
-            print(" ".join(mcmd), flush=True)
-        jobs.append((mcmd, subprocess.Popen(mcmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
-    for jcmd, pr in jobs:
-        out, err = pr.communicate()
-        if pr.returncode != 0:
-            sys.stderr.write(out + err)
-            raise RuntimeError("hipcc failed: " + " ".join(jcmd))
-        if verbose and err:
-            sys.stderr.write(err)
-    cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC"] + main_objs + objs + ["-ldl", "-o", LIB_PATH]
+            print(" ".join(cmds[-1]), flush=True)
+    try:
+        width = int(os.environ.get("MAX_JOBS", ""))
+    except ValueError:
+        width = len(cmds)
+    with ThreadPoolExecutor(max(1, min(width, len(cmds), 16))) as pool:
+        for jcmd, res in zip(cmds, pool.map(lambda c: subprocess.run(c, capture_output=True, text=True), cmds)):
+            if res.returncode != 0:
+                sys.stderr.write(res.stdout + res.stderr)
+                raise RuntimeError("hipcc failed: " + " ".join(jcmd))
+            if verbose and res.stderr:
+                sys.stderr.write(res.stderr)
+    cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-ldl", "-o", LIB_PATH]
     if verbose:
         print(" ".join(cmd), flush=True)
     res = subprocess.run(cmd, capture_output=True, text=True)

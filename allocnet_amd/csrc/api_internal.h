@@ -1,0 +1,306 @@
+// Host plumbing shared by the translation units of the C ABI (include/allocnet_amd.h).  Built by allocnet_amd/build.py:
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC
+// No torch, no Eigen.  There is no CPU fallback in this library: without a device every entry point fails with
+// ANET_ERR_NODEVICE.
+//
+// One unit per domain; each includes only the kernel headers it launches from, so every kernel is compiled in one unit:
+//   api_context.hip    context, version, memory, layout transposes, RCCL
+//   api_solve.hip      coefficient solve, sampling, wide-spread solve; trajectory evaluation, cost, normalisation, max rate
+//   api_cost_grad.hip  cost + gradient: partial gradients, adjoint, basis tables, the one-launch decision
+//   api_lbfgs.hip      L-BFGS (host, device, MVIE, MINCO), launch order, spread flags, cancel flag; FIRI and polytope depth
+//                      (FIRI launches the MVIE kernels of lbfgs_minco_persistent.h, which one unit only may include)
+//   api_qp.hip         QP assembly, settings, solve, time gradient, VJP
+//   api_voxel.hip      voxel map and route search
+//   piece_grad_unit.hip, qp_ipm_fuse_unit.hip: kernels scheduled for ILP, reached through launch functions
+// Only what two or more units use is here.  Nothing here is exported: the library's dynamic symbols stay the anet_* entry
+// points (and the kernels).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+#include <string>
+#include <vector>
+#include <rccl/rccl.h>  // types only: the library is dlopen()ed
+
+#include "../../include/allocnet_amd.h"
+#include "tuning.h"
+
+#pragma GCC visibility push(hidden)
+
+// ------------------------------------------------------------------------------------------
+// context + error plumbing
+// ------------------------------------------------------------------------------------------
+struct anet_ctx {
+  int device = -1;
+  // compute units of the device (hipDeviceAttributeMultiprocessorCount, read once in anet_create): the launch-shape thresholds
+  // were measured on the 256 CUs of an MI355X in SPX mode and are scaled by cus / 256 (tuning.h, PerCu)
+  int cus = 256;
+  hipStream_t stream = nullptr;
+  std::string err;
+  // grow-only device scratch for the host (trajectory-major) entry points
+  void *scratch = nullptr;
+  size_t scratch_bytes = 0;
+  // L-BFGS completion polling: device counter + pinned host mirror
+  int *d_counter = nullptr;
+  int *h_counter = nullptr;          // two pinned ints (polls alternate)
+  hipEvent_t poll_ev[2] = {nullptr, nullptr};
+  // pinned host staging for single-trajectory calls (inputs are packed and sent with ONE copy)
+  double *h_pack = nullptr;
+  size_t h_pack_doubles = 0;
+  // cancel word of the one-launch L-BFGS (anet_set_cancel_flag), device-visible, owned by the caller
+  const int32_t *cancel_flag = nullptr;
+  // RCCL communicator for the all-gather of costs
+  ncclComm_t comm = nullptr;
+  int comm_ranks = 0;
+  // basis tables of k_piece_grad, one per (order, res) ever used: never rebuilt, never freed before anet_destroy
+  // (a launch on another stream may still be reading one), built on the caller's stream
+  struct BasisTable {
+    int s, res;
+    double *d;
+    hipStream_t built_on;
+    hipEvent_t ready;
+  };
+  std::vector<BasisTable> tabs;
+  // tables of k_qp_ipm, one per (order, res, m34) ever used (csrc/qp_ipm.h k_qp_ipm_tables): same lifetime rules
+  struct IpmTable {
+    int s, res;
+    double m34;
+    double *d;
+    hipStream_t built_on;
+    hipEvent_t ready;
+  };
+  std::vector<IpmTable> ipm_tabs;
+};
+
+extern thread_local std::string g_err;  // errors raised without a context (defined in api_context.hip)
+
+inline int fail(anet_ctx *ctx, int code, const std::string &msg) {
+  if (ctx) ctx->err = msg;
+  g_err = msg;
+  return code;
+}
+inline int hip_fail(anet_ctx *ctx, hipError_t e, const char *what) {
+  return fail(ctx, ANET_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+#define ANET_HIP(ctx, call)                                   \
+  do {                                                        \
+    hipError_t e_ = (call);                                   \
+    if (e_ != hipSuccess) return hip_fail(ctx, e_, #call);    \
+  } while (0)
+
+// Every entry point makes the context's device current first: allocations made inside *_dev calls (counters, basis
+// tables) and the launches must land on the context's GPU, not on whatever device the calling thread used last.  The
+// caller's current device is put back on the way out (a multi-GPU torch process keeps allocating on ITS device), and
+// nothing is switched when the context's device is current already.
+struct DeviceGuard {
+  int prev = -1;
+  ~DeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+#define ANET_ON_DEVICE(ctx)                                                   \
+  DeviceGuard anet_device_guard_;                                             \
+  do {                                                                        \
+    if (!(ctx)) return fail(nullptr, ANET_ERR_INVALID, "ctx is NULL");        \
+    int cur_ = -1;                                                            \
+    ANET_HIP(ctx, hipGetDevice(&cur_));                                       \
+    if (cur_ != (ctx)->device) {                                              \
+      ANET_HIP(ctx, hipSetDevice((ctx)->device));                             \
+      anet_device_guard_.prev = cur_;                                         \
+    }                                                                         \
+  } while (0)
+
+inline int ensure_scratch(anet_ctx *ctx, size_t bytes) {
+  if (bytes <= ctx->scratch_bytes) return ANET_OK;
+  if (ctx->scratch) {
+    hipError_t e = hipFree(ctx->scratch);
+    ctx->scratch = nullptr;
+    ctx->scratch_bytes = 0;
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipFree(scratch)");
+  }
+  hipError_t e = hipMalloc(&ctx->scratch, bytes);
+  if (e != hipSuccess) {
+    ctx->scratch = nullptr;
+    return fail(ctx, ANET_ERR_NOMEM, std::string("hipMalloc(scratch): ") + hipGetErrorString(e));
+  }
+  ctx->scratch_bytes = bytes;
+  return ANET_OK;
+}
+
+inline int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+
+// Per-context tables (basis rows of k_piece_grad per (order, res); tables of k_qp_ipm per (order, res, m34)) live until
+// anet_destroy; their number is bounded, and a table whose build fails half-way is released, not leaked.
+constexpr size_t kMaxTablesPerContext = 256;
+inline int new_table(anet_ctx *ctx, size_t bytes, double **d, hipEvent_t *ready) {
+  *d = nullptr;
+  *ready = nullptr;
+  hipError_t e = hipMalloc((void **)d, bytes);
+  if (e != hipSuccess) {
+    *d = nullptr;
+    return fail(ctx, ANET_ERR_NOMEM, std::string("hipMalloc(table): ") + hipGetErrorString(e));
+  }
+  e = hipEventCreateWithFlags(ready, hipEventDisableTiming);
+  if (e != hipSuccess) {
+    (void)hipFree(*d);
+    *d = nullptr;
+    *ready = nullptr;
+    return hip_fail(ctx, e, "hipEventCreateWithFlags(table)");
+  }
+  return ANET_OK;
+}
+inline void drop_table(double *d, hipEvent_t ready) {
+  if (d) (void)hipFree(d);
+  if (ready) (void)hipEventDestroy(ready);
+}
+
+// max T / min T inside one trajectory above which the host entry point of the coefficient solve switches to the pivoted
+// collocation solve (minco_dense_kernels.h)
+constexpr double kWideSpread = 50.0;
+
+int ensure_counter(anet_ctx *ctx);  // the L-BFGS / route-search completion poll: device counter, pinned mirror, events
+
+// (callers make the context's device current first: ANET_ON_DEVICE in front of every call)
+inline int check_solve_args(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batch) {
+  if (!ctx) return fail(nullptr, ANET_ERR_INVALID, "ctx is NULL");
+  if (s < 2 || s > 4) return fail(ctx, ANET_ERR_INVALID, "order s must be 2, 3 or 4");
+  if (c < 1 || c > s) return fail(ctx, ANET_ERR_INVALID, "boundary derivative count c must be in [1, s]");
+  if (n_pieces < 1 || n_pieces > ANET_MAX_PIECES)
+    return fail(ctx, ANET_ERR_INVALID, "piece count must be in [1, ANET_MAX_PIECES]");
+  if (batch < 0) return fail(ctx, ANET_ERR_INVALID, "negative batch");
+  return ANET_OK;
+}
+
+inline int check_penalty(anet_ctx *ctx, const anet_penalty *pen) {
+  if (!pen) return ANET_OK;
+  if (!(pen->smooth_mu > 0.0)) return fail(ctx, ANET_ERR_INVALID, "anet_penalty.smooth_mu must be > 0");
+  if (pen->res < 1) return fail(ctx, ANET_ERR_INVALID, "anet_penalty.res must be >= 1");
+  if (pen->poly_rows < 0 || pen->poly_rows > ANET_MAX_POLY_ROWS)
+    return fail(ctx, ANET_ERR_INVALID, "anet_penalty.poly_rows must be in [0, ANET_MAX_POLY_ROWS]");
+  return ANET_OK;
+}
+
+// Host (trajectory-major) wrappers: stage -> batch-minor -> kernel -> back.
+struct Stager {
+  anet_ctx *ctx;
+  int64_t batch, ld;
+  double *stage;   // batch * max_fields doubles
+  double *cursor;  // next free batch-minor region
+  int upload(const double *host, int64_t nf, double **dev) {
+    *dev = cursor;
+    cursor += nf * ld;
+    if (nf == 0) return ANET_OK;
+    if (batch == 1) {
+      // one trajectory: both layouts coincide (ld = 1), no transpose kernel; the inputs are packed into
+      // pinned memory and go out with a single copy when the first output region is reserved
+      if (!pack_base) pack_base = *dev;
+      const size_t off = (size_t)(*dev - pack_base);
+      if (off + (size_t)nf > ctx->h_pack_doubles) {
+        const size_t want = (off + (size_t)nf) * 2 + 1024;
+        double *np_ = nullptr;
+        hipError_t e1 = hipHostMalloc((void **)&np_, sizeof(double) * want, hipHostMallocDefault);
+        if (e1 != hipSuccess) return hip_fail(ctx, e1, "hipHostMalloc(pack)");
+        if (ctx->h_pack) {
+          memcpy(np_, ctx->h_pack, sizeof(double) * off);
+          (void)hipHostFree(ctx->h_pack);
+        }
+        ctx->h_pack = np_;
+        ctx->h_pack_doubles = want;
+      }
+      memcpy(ctx->h_pack + off, host, sizeof(double) * nf);
+      pack_doubles = off + (size_t)nf;
+      return ANET_OK;
+    }
+    hipError_t e = hipMemcpyAsync(stage, host, sizeof(double) * batch * nf, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipMemcpyAsync(H2D)");
+    return anet_to_batch_minor_dev(ctx, batch, nf, ld, stage, *dev, ctx->stream);
+  }
+  double *pack_base = nullptr;
+  size_t pack_doubles = 0;
+  int flush() {  // send the packed single-trajectory inputs (no-op otherwise)
+    if (pack_base && pack_doubles) {
+      hipError_t e = hipMemcpyAsync(pack_base, ctx->h_pack, sizeof(double) * pack_doubles, hipMemcpyHostToDevice, ctx->stream);
+      pack_doubles = 0;
+      if (e != hipSuccess) return hip_fail(ctx, e, "hipMemcpyAsync(H2D packed)");
+    }
+    return ANET_OK;
+  }
+  double *reserve(int64_t nf) {  // called after all uploads and before the kernels in every entry point
+    (void)flush();
+    double *p = cursor;
+    cursor += nf * ld;
+    return p;
+  }
+  int download(const double *dev, int64_t nf, double *host) {
+    if (batch == 1) {
+      hipError_t e1 = hipMemcpyAsync(host, dev, sizeof(double) * nf, hipMemcpyDeviceToHost, ctx->stream);
+      if (e1 != hipSuccess) return hip_fail(ctx, e1, "hipMemcpyAsync(D2H)");
+      e1 = hipStreamSynchronize(ctx->stream);
+      if (e1 != hipSuccess) return hip_fail(ctx, e1, "hipStreamSynchronize");
+      return ANET_OK;
+    }
+    int rc = anet_to_traj_major_dev(ctx, batch, nf, ld, dev, stage, ctx->stream);
+    if (rc) return rc;
+    hipError_t e = hipMemcpyAsync(host, stage, sizeof(double) * batch * nf, hipMemcpyDeviceToHost, ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipMemcpyAsync(D2H)");
+    // the staging buffer is reused by the next transfer
+    e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipStreamSynchronize");
+    return ANET_OK;
+  }
+};
+inline int make_stager(anet_ctx *ctx, int64_t batch, int64_t max_field, int64_t total_fields, Stager *st) {
+  // (the entry point that stages has made the context's device current: ANET_ON_DEVICE)
+  const int64_t ld = batch == 1 ? 1 : anet_recommended_ld(batch);
+  int rc = ensure_scratch(ctx, sizeof(double) * (size_t)(batch * max_field + total_fields * ld));
+  if (rc) return rc;
+  st->ctx = ctx; st->batch = batch; st->ld = ld;
+  st->stage = (double *)ctx->scratch;
+  st->cursor = st->stage + batch * max_field;
+  st->pack_base = nullptr;
+  st->pack_doubles = 0;
+  return ANET_OK;
+}
+
+// Launch order for anet_lbfgs_minco_ordered_dev from the evaluation counts of a previous solve: a counting sort into 4096
+// buckets of 16 evaluations, longest first (the order inside a bucket is whatever the atomics make it: irrelevant here).
+constexpr int kOrderBuckets = 4096;
+
+// the counting sort of the launch order (api_lbfgs.hip): shift 4 for evaluation counts, 0 for Newton-step counts
+int launch_order_impl(anet_ctx *ctx, int64_t batch, const int32_t *counts, int32_t *launch_order, int32_t *work, void *stream,
+                      int shift);
+
+// The tail of the workspace of a solve that can run in two launches (the one-launch L-BFGS, the interior-point QP): the parked
+// state of every problem (`per` doubles each), then its score and the order of the second launch (int32 rows of ld, each padded
+// to whole doubles) and the bins of the counting sort.  doubles() is what the _workspace functions add for it, carve() is how
+// the _dev_impls cut it.
+struct ResumeTail {
+  int64_t per, ld;
+  double *cont;
+  int32_t *score, *order, *bins;
+  static int64_t doubles(int64_t per, int64_t ld) { return per * ld + ld + 2 + kOrderBuckets / 2; }
+  void carve(double *w) {
+    cont = w;
+    score = (int32_t *)(cont + per * ld);
+    order = score + ld + (ld & 1);
+    bins = order + ld + (ld & 1);
+  }
+};
+
+// Between the two launches of a two-launch solve, whose first launch parked the unfinished problems in t.cont: score them
+// (score(t.score) enqueues the solver's score kernel), counting-sort the scores into the order of the second launch, longest-
+// expected first, and enqueue that launch (resume(t.order)).
+template <class Score, class Resume>
+int resume_parked(anet_ctx *ctx, int64_t batch, const ResumeTail &t, hipStream_t st, Score &&score, Resume &&resume) {
+  score(t.score);
+  const int rc = launch_order_impl(ctx, batch, t.score, t.order, t.bins, st, 0);
+  return rc ? rc : resume(t.order);
+}
+
+// cost + gradient of a batch (api_cost_grad.hip); tau != nullptr: the durations are T = forward_T(tau) and gradT is returned as
+// dJ/dtau (the L-BFGS driver)
+int cost_grad_dev_impl(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batch, int64_t ld, const double *head, const double *tail,
+                       const double *wps, const double *T, const double *hpolys, const anet_penalty *pen, double *work, double *cost,
+                       double *gradP, double *gradT, double *coeffs_out, void *stream, const double *tau);
+
+#pragma GCC visibility pop

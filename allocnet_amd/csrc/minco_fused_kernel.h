@@ -23,7 +23,7 @@
 // workgroup of G trajectories takes a smaller G, and the lanes that frees split the SAMPLES of a piece further: Q = 128 / (G NB)
 // lane pairs per (trajectory, piece), 2 Q lanes taking every 2 Q-th sample each (the basis table from a copy in LDS, since the
 // sample index differs from lane to lane); their partial gradients are added in a fixed order through LDS.  For batches that fill the chip the three
-// streaming kernels remain the better shape (the host picks: allocnet_amd.hip cost_grad_dev_impl).
+// streaming kernels remain the better shape (the host picks: api_cost_grad.hip cost_grad_dev_impl).
 #pragma once
 #include "minco_kernels.h"
 #include "piece_grad_mx.h"

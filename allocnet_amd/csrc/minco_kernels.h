@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "minco_core.h"
 
 namespace anet {
@@ -288,22 +289,9 @@ struct PieceGradArgs {
 // + wa sum phi(+-a-amax)] sampled at t = j T/res: the rows of the reference's inequality block
 // (qp_solver.hpp:244-296 / min_traj_opt.py:535-613) turned into a smoothed-L1 penalty.
 // Basis rows in normalised time, tab[j][d][col] = k!/(k-d)! tau_j^(k-d) (k = D-1-col, tau_j = j/res): built once per
-// (order, res) into a small device buffer.  k_piece_grad reads it through a `const __restrict__` kernel argument with a
-// wave-uniform index, i.e. as SCALAR loads: the values arrive in SGPRs and feed the FMAs directly, no LDS traffic and
-// no vector registers for the table.
-static __global__ void __launch_bounds__(256) k_build_basis_table(double *tab, int res, int D) {  // (static: this header is in two translation units)
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= res * 4 * D) return;
-  const int j = e / (4 * D), d = (e / D) % 4, col = e % D, k = D - 1 - col;
-  const double tau = (double)j / (double)res;
-  double v = 0.0;
-  if (k >= d) {
-    v = 1.0;
-    for (int q = 0; q < d; ++q) v *= (double)(k - q);
-    for (int q = 0; q < k - d; ++q) v *= tau;
-  }
-  tab[e] = v;
-}
+// (order, res) into a small device buffer (k_build_basis_table, api_cost_grad.hip).  k_piece_grad reads it through a
+// `const __restrict__` kernel argument with a wave-uniform index, i.e. as SCALAR loads: the values arrive in SGPRs and feed
+// the FMAs directly, no LDS traffic and no vector registers for the table.
 
 // SPLIT (small batches): TWO adjacent lanes per (trajectory, piece).  Lane 0 of the pair takes the energy part and
 // the even row chunks, lane 1 the box rows and the odd chunks; the partial gradients are summed across the pair
@@ -1075,6 +1063,15 @@ void with_minco_shape(int N, int c, F &&f) {
   if (N <= 4) f(MincoShape<4>{});
   else if (N <= 8) f(MincoShape<8>{});
   else f(MincoShape<16>{});
+}
+
+// The order ladder of the host launches: f(std::integral_constant<int, S>{}) with S = s for s = 2, 3 and S = 4 otherwise (the
+// callers have checked s)
+template <class F>
+decltype(auto) with_order(int s, F &&f) {
+  if (s == 2) return f(std::integral_constant<int, 2>{});
+  if (s == 3) return f(std::integral_constant<int, 3>{});
+  return f(std::integral_constant<int, 4>{});
 }
 
 }  // namespace anet
