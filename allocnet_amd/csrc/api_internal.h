@@ -8,7 +8,7 @@
 //   api_solve.hip      coefficient solve, sampling, wide-spread solve; trajectory evaluation, cost, normalisation, max rate
 //   api_cost_grad.hip  cost + gradient: partial gradients, adjoint, basis tables, the one-launch decision
 //   api_lbfgs.hip      L-BFGS (host, device, MVIE, MINCO), launch order, spread flags, cancel flag; FIRI and polytope depth
-//                      (FIRI launches the MVIE kernels of lbfgs_minco_persistent.h, which one unit only may include)
+//                      (FIRI launches the MVIE kernels of mvie_kernels.h, which one unit only may include)
 //   api_qp.hip         QP assembly, settings, solve, time gradient, VJP
 //   api_voxel.hip      voxel map and route search
 //   piece_grad_unit.hip, qp_ipm_fuse_unit.hip: kernels scheduled for ILP, reached through launch functions

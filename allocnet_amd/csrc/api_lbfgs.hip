@@ -1,12 +1,19 @@
 // L-BFGS: parameters, the host and device optimisers, MVIE, the MINCO optimisation, launch order, spread flags, cancel flag;
 // FIRI and polytope depth, which launch the MVIE kernels of this unit (include/allocnet_amd.h).
 #include "api_internal.h"
+#include "lbfgs_kernels.h"
+#include "mvie_kernels.h"
 #include "lbfgs_minco_persistent.h"
 #include "firi_kernels.h"
 
 namespace {
 
 // ---- L-BFGS driver ----------------------------------------------------------------------------
+static anet::LbfgsP to_kernel_params(const anet_lbfgs_params &p) {
+  return anet::LbfgsP{p.mem_size, p.g_epsilon, p.past, p.delta, p.max_iterations, p.max_linesearch,
+                      p.min_step, p.max_step, p.f_dec_coeff, p.s_curv_coeff, p.cautious_factor, p.machine_prec};
+}
+
 struct LbfgsLayout {
   int n, m, npf;
   int64_t ld;
@@ -22,12 +29,24 @@ struct LbfgsLayout {
     lm_alpha = lm_ys + (int64_t)m * ld; pf = lm_alpha + (int64_t)m * ld; ds = pf + (int64_t)npf * ld;
     feval = ds + (int64_t)anet::DS_COUNT_ * ld; is = (int *)(feval + ld);
   }
+  // The kernels' view of this layout for B problems.  wave: the internal vectors (xp, gp, d, lm_s, lm_y) problem-major (element i
+  // of problem b at [i + b*n]: one wave per problem), else batch-minor (one lane per problem).  What a call site has beyond
+  // this -- variable map, step bound, cancel word, host callbacks -- it sets by field name.
+  anet::LbfgsArgs args(int64_t B, const anet_lbfgs_params &p, bool wave) const {
+    anet::LbfgsArgs a{};
+    a.n = n; a.B = B; a.ld = ld;
+    a.x = x; a.g = g; a.xp = xp; a.gp = gp; a.d = d; a.lm_s = lm_s; a.lm_y = lm_y; a.lm_ys = lm_ys; a.lm_alpha = lm_alpha;
+    a.pf = pf; a.ds = ds; a.feval = feval; a.is = is;
+    a.p = to_kernel_params(p);
+    a.vs = wave ? 1 : ld; a.ps = wave ? n : 1;
+    return a;
+  }
+  // a fresh run: every IS_* / DS_* row zero
+  hipError_t reset(hipStream_t st) const {
+    const hipError_t e = hipMemsetAsync(is, 0, sizeof(int) * anet::IS_COUNT_ * ld, st);
+    return e != hipSuccess ? e : hipMemsetAsync(ds, 0, sizeof(double) * anet::DS_COUNT_ * ld, st);
+  }
 };
-
-static anet::LbfgsP to_kernel_params(const anet_lbfgs_params &p) {
-  return anet::LbfgsP{p.mem_size, p.g_epsilon, p.past, p.delta, p.max_iterations, p.max_linesearch,
-                      p.min_step, p.max_step, p.f_dec_coeff, p.s_curv_coeff, p.cautious_factor, p.machine_prec};
-}
 
 
 // eval(): enqueue the objective at L.x -> L.feval, L.g (for all problems).  The loop advances every
@@ -41,17 +60,15 @@ static int lbfgs_drive(anet_ctx *ctx, LbfgsLayout &L, int64_t B, const anet_lbfg
                        int sb_on = 0, double sb_xmin = 0.0, const int32_t *cancel = nullptr) {
   int rc = ensure_counter(ctx);
   if (rc) return rc;
-  if (reset) {  // (a caller that pre-marks problems as finished resets the state itself)
-    ANET_HIP(ctx, hipMemsetAsync(L.is, 0, sizeof(int) * anet::IS_COUNT_ * L.ld, st));
-    ANET_HIP(ctx, hipMemsetAsync(L.ds, 0, sizeof(double) * anet::DS_COUNT_ * L.ld, st));
-  }
+  if (reset) ANET_HIP(ctx, L.reset(st));  // (a caller that pre-marks problems as finished resets the state itself)
   // one wave per problem (DPP reductions, internal vectors problem-major) whenever the problem fits a wave's registers, at every
   // batch size -- at 131072 x 29 variables the lane-per-problem update kernel took 1.67 ms per tick (three times the objective
   // evaluation), the wave kernel 0.4 ms --; otherwise one lane per problem (internal vectors batch-minor)
   const bool wave = L.n <= 128 && prm.mem_size <= 64;
-  anet::LbfgsArgs a{L.n, B, L.ld, L.x, L.g, L.xp, L.gp, L.d, L.lm_s, L.lm_y, L.lm_ys, L.lm_alpha, L.pf, L.ds,
-                    L.feval, L.is, to_kernel_params(prm), nullptr, wave ? 1 : L.ld, wave ? L.n : 1, map_T, map_nw,
-                    sb_on, map_nw, sb_xmin, (const int *)cancel};
+  anet::LbfgsArgs a = L.args(B, prm, wave);
+  a.map_T = map_T; a.map_nw = map_nw;
+  a.sb_on = sb_on; a.sb_lo = map_nw; a.sb_xmin = sb_xmin;
+  a.cancel = (const int *)cancel;
   const dim3 grid(wave ? (unsigned)B : (unsigned)((B + 63) / 64)), block(64);
   const int poll = 8;
   int group = 0;
@@ -60,34 +77,21 @@ static int lbfgs_drive(anet_ctx *ctx, LbfgsLayout &L, int64_t B, const anet_lbfg
     const bool check = ((it + 1) % poll == 0) || it + 1 == max_evals;
     if (check) ANET_HIP(ctx, hipMemsetAsync(ctx->d_counter, 0, sizeof(int), st));
     a.n_active = check ? ctx->d_counter : nullptr;
-    if (wave) {
-      auto shape = [&](int waves, dim3 &g, dim3 &bl) {
-        g = dim3((unsigned)((B + waves - 1) / waves));
-        bl = dim3(64u * waves);
-      };
-      dim3 gw, bw;
-      const bool one = L.n <= 64;  // one variable per lane: half the registers
-      if (a.p.mem_size <= 8 && L.n <= 32) {  // two problems per wave
-        const int waves = anet::LbfgsWaveShape<8>::kWaves;
-        gw = dim3((unsigned)((B + 2 * waves - 1) / (2 * waves)));
-        bw = dim3(64u * waves);
-        hipLaunchKernelGGL((anet::k_lbfgs_update_wave<8, 1, true>), gw, bw, 0, st, a);
-      } else if (a.p.mem_size <= 8) {
-        shape(anet::LbfgsWaveShape<8>::kWaves, gw, bw);
-        if (one) hipLaunchKernelGGL((anet::k_lbfgs_update_wave<8, 1>), gw, bw, 0, st, a);
-        else hipLaunchKernelGGL((anet::k_lbfgs_update_wave<8, 2>), gw, bw, 0, st, a);
-      } else if (a.p.mem_size <= 20) {
-        shape(anet::LbfgsWaveShape<20>::kWaves, gw, bw);
-        if (one) hipLaunchKernelGGL((anet::k_lbfgs_update_wave<20, 1>), gw, bw, 0, st, a);
-        else hipLaunchKernelGGL((anet::k_lbfgs_update_wave<20, 2>), gw, bw, 0, st, a);
-      } else {
-        shape(anet::LbfgsWaveShape<0>::kWaves, gw, bw);
-        if (one) hipLaunchKernelGGL((anet::k_lbfgs_update_wave<0, 1>), gw, bw, 0, st, a);
-        else hipLaunchKernelGGL((anet::k_lbfgs_update_wave<0, 2>), gw, bw, 0, st, a);
-      }
-    } else {
-      hipLaunchKernelGGL(anet::k_lbfgs_update, grid, block, 0, st, a);
-    }
+    // `waves` waves per workgroup, `per` problems per wave
+    auto launch = [&](auto kernel, int waves, int per) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)((B + per * waves - 1) / (per * waves))), dim3(64u * waves), 0, st, a);
+    };
+    const int m = a.p.mem_size;
+    const bool one = L.n <= 64;  // one variable per lane: half the registers
+    constexpr int W8 = anet::LbfgsWaveShape<8>::kWaves, W20 = anet::LbfgsWaveShape<20>::kWaves, W0 = anet::LbfgsWaveShape<0>::kWaves;
+    if (!wave) hipLaunchKernelGGL(anet::k_lbfgs_update, grid, block, 0, st, a);
+    else if (m <= 8 && L.n <= 32) launch(anet::k_lbfgs_update_wave<8, 1, true>, W8, 2);  // two problems per wave
+    else if (m <= 8 && one) launch(anet::k_lbfgs_update_wave<8, 1>, W8, 1);
+    else if (m <= 8) launch(anet::k_lbfgs_update_wave<8, 2>, W8, 1);
+    else if (m <= 20 && one) launch(anet::k_lbfgs_update_wave<20, 1>, W20, 1);
+    else if (m <= 20) launch(anet::k_lbfgs_update_wave<20, 2>, W20, 1);
+    else if (one) launch(anet::k_lbfgs_update_wave<0, 1>, W0, 1);
+    else launch(anet::k_lbfgs_update_wave<0, 2>, W0, 1);
     ANET_HIP(ctx, hipGetLastError());
     if (check) {
       const int slot = group & 1;
@@ -102,6 +106,25 @@ static int lbfgs_drive(anet_ctx *ctx, LbfgsLayout &L, int64_t B, const anet_lbfg
   }
   ANET_HIP(ctx, hipStreamSynchronize(st));
   return ANET_OK;
+}
+
+// The whole MVIE optimisation (nine variables, M rows) in one launch, one wave per problem: everything in registers when it
+// fits (<= 128 rows, mem_size <= 20, past <= 64; k_lbfgs_mvie_resident), else the state goes through memory
+// (k_lbfgs_mvie_persistent, mem_size <= 64).  FIRI's call is the mem_size = 18 row of this ladder.
+static void launch_mvie_one_launch(const anet::LbfgsArgs &la, const anet::MvieArgs &ma, int max_evals, hipStream_t st) {
+  const int m = la.p.mem_size, M = ma.M;
+  const int64_t batch = la.B;
+  auto launch = [&](auto kernel, int waves) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((batch + waves - 1) / waves)), dim3(64u * waves), 0, st, la, ma, max_evals);
+  };
+  const bool resident = M <= 128 && m <= 20 && la.p.past <= 64 && !anet::env_set(anet::Tuning::mvie_state_in_memory);
+  if (resident && m <= 8 && M <= 64) launch(anet::k_lbfgs_mvie_resident<8, 1>, 1);
+  else if (resident && m <= 8) launch(anet::k_lbfgs_mvie_resident<8, 2>, 1);
+  else if (resident && M <= 64) launch(anet::k_lbfgs_mvie_resident<20, 1>, 1);
+  else if (resident) launch(anet::k_lbfgs_mvie_resident<20, 2>, 1);
+  else if (m <= 8) launch(anet::k_lbfgs_mvie_persistent<8>, anet::LbfgsWaveShape<8>::kWaves);
+  else if (m <= 20) launch(anet::k_lbfgs_mvie_persistent<20>, anet::LbfgsWaveShape<20>::kWaves);
+  else launch(anet::k_lbfgs_mvie_persistent<0>, anet::LbfgsWaveShape<0>::kWaves);
 }
 
 // (shift 4: evaluation counts of an L-BFGS run, up to 65535; shift 0: Newton-step counts of the interior point, up to 4095)
@@ -234,6 +257,16 @@ const char *anet_lbfgs_strerror(int code) {
   }
 }
 
+// status / iters / evals rows of d_res (k_lbfgs_results: ld int32 each) and the cost -> the caller's host arrays
+static int download_results(anet_ctx *ctx, int64_t batch, int64_t ld, const int *d_res, const double *d_cost, int32_t *status,
+                            int32_t *iters, int32_t *evals, double *cost, hipStream_t s0) {
+  if (status) ANET_HIP(ctx, hipMemcpyAsync(status, d_res, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
+  if (iters) ANET_HIP(ctx, hipMemcpyAsync(iters, d_res + ld, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
+  if (evals) ANET_HIP(ctx, hipMemcpyAsync(evals, d_res + 2 * ld, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
+  if (cost) ANET_HIP(ctx, hipMemcpyAsync(cost, d_cost, sizeof(double) * batch, hipMemcpyDeviceToHost, s0));
+  return ANET_OK;
+}
+
 static int check_lbfgs(anet_ctx *ctx, int n, const anet_lbfgs_params *params, int max_evals) {
   const int code = anet_lbfgs_check_params(n, params);
   if (code) return fail(ctx, ANET_ERR_INVALID, std::string("lbfgs parameters rejected: ") + anet_lbfgs_strerror(code));
@@ -268,22 +301,8 @@ int anet_lbfgs_mvie(anet_ctx *ctx, int64_t batch, int M, const double *A, double
   const dim3 grid((unsigned)((batch + 63) / 64)), block(64);
   if (params->mem_size <= 64) {
     // one wave per problem, the whole optimisation in one launch (k_lbfgs_mvie_persistent)
-    ANET_HIP(ctx, hipMemsetAsync(L.is, 0, sizeof(int) * anet::IS_COUNT_ * L.ld, s0));
-    ANET_HIP(ctx, hipMemsetAsync(L.ds, 0, sizeof(double) * anet::DS_COUNT_ * L.ld, s0));
-    anet::LbfgsArgs la{L.n, batch, L.ld, L.x, L.g, L.xp, L.gp, L.d, L.lm_s, L.lm_y, L.lm_ys, L.lm_alpha, L.pf, L.ds,
-                       L.feval, L.is, to_kernel_params(*params), nullptr, 1, L.n, nullptr, 0};
-    auto launch = [&](auto kernel, int waves) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)((batch + waves - 1) / waves)), dim3(64u * waves), 0, s0, la, ma, max_evals);
-    };
-    // everything in registers when it fits (<= 128 rows, mem_size <= 20, past <= 64); else the state goes through memory
-    const bool resident = M <= 128 && m <= 20 && params->past <= 64 && !anet::env_set(anet::Tuning::mvie_state_in_memory);
-    if (resident && m <= 8 && M <= 64) launch(anet::k_lbfgs_mvie_resident<8, 1>, 1);
-    else if (resident && m <= 8) launch(anet::k_lbfgs_mvie_resident<8, 2>, 1);
-    else if (resident && M <= 64) launch(anet::k_lbfgs_mvie_resident<20, 1>, 1);
-    else if (resident) launch(anet::k_lbfgs_mvie_resident<20, 2>, 1);
-    else if (m <= 8) launch(anet::k_lbfgs_mvie_persistent<8>, anet::LbfgsWaveShape<8>::kWaves);
-    else if (m <= 20) launch(anet::k_lbfgs_mvie_persistent<20>, anet::LbfgsWaveShape<20>::kWaves);
-    else launch(anet::k_lbfgs_mvie_persistent<0>, anet::LbfgsWaveShape<0>::kWaves);
+    ANET_HIP(ctx, L.reset(s0));
+    launch_mvie_one_launch(L.args(batch, *params, true), ma, max_evals, s0);
     ANET_HIP(ctx, hipGetLastError());
   } else {
     rc = lbfgs_drive(ctx, L, batch, *params, max_evals, s0, [&]() -> int {
@@ -296,10 +315,7 @@ int anet_lbfgs_mvie(anet_ctx *ctx, int64_t batch, int M, const double *A, double
   hipLaunchKernelGGL(k_lbfgs_results, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s0, L.is, L.ds, batch,
                      st.ld, d_res, d_res + st.ld, d_res + 2 * st.ld, L.feval);
   ANET_HIP(ctx, hipGetLastError());
-  if (status) ANET_HIP(ctx, hipMemcpyAsync(status, d_res, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
-  if (iters) ANET_HIP(ctx, hipMemcpyAsync(iters, d_res + st.ld, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
-  if (evals) ANET_HIP(ctx, hipMemcpyAsync(evals, d_res + 2 * st.ld, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
-  if (f) ANET_HIP(ctx, hipMemcpyAsync(f, L.feval, sizeof(double) * batch, hipMemcpyDeviceToHost, s0));
+  if ((rc = download_results(ctx, batch, st.ld, d_res, L.feval, status, iters, evals, f, s0))) return rc;
   return st.download(L.x, n, x);
 }
 
@@ -376,12 +392,11 @@ int anet_lbfgs_optimize_host(anet_ctx *ctx, int n, double *x, double *f, anet_lb
   int *d_cancel = (int *)((double *)own.p + wd + 2);
   hipStream_t st = ctx->stream;
   std::vector<double> hg((size_t)n), hxp((size_t)n), hd((size_t)n);
-  ANET_HIP(ctx, hipMemsetAsync(L.is, 0, sizeof(int) * anet::IS_COUNT_, st));
-  ANET_HIP(ctx, hipMemsetAsync(L.ds, 0, sizeof(double) * anet::DS_COUNT_, st));
+  ANET_HIP(ctx, L.reset(st));
   ANET_HIP(ctx, hipMemsetAsync(d_cancel, 0, sizeof(int), st));
   ANET_HIP(ctx, hipMemcpyAsync(L.x, x, sizeof(double) * n, hipMemcpyHostToDevice, st));
-  anet::LbfgsArgs a{n, 1, 1, L.x, L.g, L.xp, L.gp, L.d, L.lm_s, L.lm_y, L.lm_ys, L.lm_alpha, L.pf, L.ds, L.feval, L.is,
-                    to_kernel_params(*params), nullptr, 1, 1, nullptr, 0, 0, 0, 0.0, d_cancel};
+  anet::LbfgsArgs a = L.args(1, *params, false);
+  a.cancel = d_cancel;
   a.host_pg = proc_progress ? 1 : 0;
   a.host_sb = proc_stepbound ? 1 : 0;
   int his[anet::IS_COUNT_];
@@ -455,8 +470,9 @@ __global__ void k_lbfgs_resume_score(const int *is, const double *cont, int64_t 
   if (b >= B) return;
   int sc = 0;
   if (is[(int64_t)anet::IS_DONE * ld + b] == 0) {
-    const double *u = cont + b * (int64_t)anet::kPersistContDoubles + 22 * 64;
-    const double fx = fabs(u[8]) + 1e-300, dec = fmax((u[23] - u[8]) / fx, 1e-16), gn = sqrt(fmax(u[24], 0.0)) / fx;
+    const double *u = anet::parked_uniform(cont + b * (int64_t)anet::kPersistContDoubles);
+    const double fx = fabs(u[anet::PARK_U_FX]) + 1e-300, dec = fmax((u[anet::PARK_U_F_HALF] - u[anet::PARK_U_FX]) / fx, 1e-16),
+                 gn = sqrt(fmax(u[anet::PARK_U_GN2], 0.0)) / fx;
     double v = 4000.0 + 150.0 * (log10(fmax(gn, 1e-16)) + log10(dec));
     if (!(v == v)) v = 4000.0;
     sc = (int)fmin(fmax(v, 1.0), 4000.0);
@@ -554,6 +570,19 @@ static int lbfgs_minco_dev_impl(anet_ctx *ctx, int s, int c, int n_pieces, int64
   // snap 2.3 s in one launch against 4.1 s in lockstep, 131072 x 16-segment jerk 3.5 s against 10.0 s.  So one launch
   // at any batch; callers with a small fixed evaluation budget at a huge batch ask for the lockstep shape (ANET_OPT_LOCKSTEP).
   const int Mrows = (pen && hpolys) ? pen->poly_rows : 0;
+  // the minimum-duration bound of either shape, in the variable tau (gcopter's backwardT, minco_core.h backward_T)
+  const int step_bound = (min_duration > 0.0 && nt > 0) ? 1 : 0;
+  const double tau_min = min_duration > 1.0 ? sqrt(2.0 * min_duration - 1.0) - 1.0
+                                            : (min_duration > 0.0 ? 1.0 - sqrt(2.0 / min_duration - 1.0) : 0.0);
+  // final parameters (x may have been reverted by a failed line search) and outputs
+  auto finish = [&]() -> int {
+    mp.mode = 1;
+    hipLaunchKernelGGL(anet::k_minco_map, gmap, b256, 0, st, mp);
+    ANET_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_lbfgs_results, g256, b256, 0, st, L.is, L.ds, batch, ld, status, iters, evals, cost);
+    ANET_HIP(ctx, hipGetLastError());
+    return coeffs_out ? final_coeffs(ctx, s, c, N, batch, ld, head, tail, wps, T, coeffs_out, st) : ANET_OK;
+  };
   const size_t row_bytes = sizeof(double) * anet::persist_lds_row_doubles(N, Mrows);
   if (!(opt_flags & ANET_OPT_LOCKSTEP) && (s == 3 || s == 4) && n <= 64 &&
       params->mem_size <= 8 && params->past <= 64) {
@@ -566,9 +595,9 @@ static int lbfgs_minco_dev_impl(anet_ctx *ctx, int s, int c, int n_pieces, int64
     else pa.pp = anet::Penalty{0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 1, 0};
     pa.inv_mu = 1.0 / pa.pp.mu; pa.inv_res = 1.0 / (double)pa.pp.res;
     pa.p = to_kernel_params(*params);
-    pa.step_bound = (min_duration > 0.0 && nt > 0) ? 1 : 0;  // (gcopter's backwardT, minco_core.h backward_T)
+    pa.step_bound = step_bound;
     pa.cancel = (const int *)ctx->cancel_flag;
-    pa.tau_min = min_duration > 1.0 ? sqrt(2.0 * min_duration - 1.0) - 1.0 : (min_duration > 0.0 ? 1.0 - sqrt(2.0 / min_duration - 1.0) : 0.0);
+    pa.tau_min = tau_min;
 #ifdef ANET_PERSIST_PROF
     static long long *d_prof = nullptr;
     if (!d_prof) ANET_HIP(ctx, hipMalloc((void **)&d_prof, 16 * sizeof(long long)));
@@ -645,30 +674,16 @@ static int lbfgs_minco_dev_impl(anet_ctx *ctx, int s, int c, int n_pieces, int64
                 h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[9]);
       }
 #endif
-      mp.mode = 1;
-      hipLaunchKernelGGL(anet::k_minco_map, gmap, b256, 0, st, mp);
-      ANET_HIP(ctx, hipGetLastError());
-      hipLaunchKernelGGL(k_lbfgs_results, g256, b256, 0, st, L.is, L.ds, batch, ld, status, iters, evals, cost);
-      ANET_HIP(ctx, hipGetLastError());
-      return coeffs_out ? final_coeffs(ctx, s, c, N, batch, ld, head, tail, wps, T, coeffs_out, st) : ANET_OK;
+      return finish();
     }
   }
   // the lockstep shape: the same minimum-duration bound (one maximum over the duration variables per iteration) and the
   // same cancel word, looked at after every successful line search (lbfgs.hpp:557-565, 580-587)
-  const double tau_min = min_duration > 1.0 ? sqrt(2.0 * min_duration - 1.0) - 1.0
-                                            : (min_duration > 0.0 ? 1.0 - sqrt(2.0 / min_duration - 1.0) : 0.0);
   rc = lbfgs_drive(ctx, L, batch, *params, max_evals, st, [&]() -> int {
     return cost_grad_dev_impl(ctx, s, c, N, batch, ld, head, tail, wps_eval, T, hpolys, pen, w_cg, L.feval, gP_out,
                               gT_out, nullptr, st, tau);
-  }, nt ? T : nullptr, nw, true, (min_duration > 0.0 && nt > 0) ? 1 : 0, tau_min, ctx->cancel_flag);
-  if (rc) return rc;
-  // final parameters (x may have been reverted by a failed line search) and outputs
-  mp.mode = 1;
-  hipLaunchKernelGGL(anet::k_minco_map, gmap, b256, 0, st, mp);
-  ANET_HIP(ctx, hipGetLastError());
-  hipLaunchKernelGGL(k_lbfgs_results, g256, b256, 0, st, L.is, L.ds, batch, ld, status, iters, evals, cost);
-  ANET_HIP(ctx, hipGetLastError());
-  return coeffs_out ? final_coeffs(ctx, s, c, N, batch, ld, head, tail, wps, T, coeffs_out, st) : ANET_OK;
+  }, nt ? T : nullptr, nw, true, step_bound, tau_min, ctx->cancel_flag);
+  return rc ? rc : finish();
 }
 
 int anet_lbfgs_minco_ordered_dev(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batch, int64_t ld,
@@ -729,10 +744,7 @@ static int lbfgs_minco_host_impl(anet_ctx *ctx, int s, int c, int n_pieces, int6
                             d_res + 2 * st.ld, ctx->stream);
   if (rc) return rc;
   hipStream_t s0 = ctx->stream;
-  if (status) ANET_HIP(ctx, hipMemcpyAsync(status, d_res, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
-  if (iters) ANET_HIP(ctx, hipMemcpyAsync(iters, d_res + st.ld, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
-  if (evals) ANET_HIP(ctx, hipMemcpyAsync(evals, d_res + 2 * st.ld, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
-  if (cost) ANET_HIP(ctx, hipMemcpyAsync(cost, d_cost, sizeof(double) * batch, hipMemcpyDeviceToHost, s0));
+  if ((rc = download_results(ctx, batch, st.ld, d_res, d_cost, status, iters, evals, cost, s0))) return rc;
   if (N > 1 && (rc = st.download(d_wps, (int64_t)(N - 1) * 3, wps))) return rc;
   if ((rc = st.download(d_T, N, T))) return rc;
   if (coeffs_out && (rc = st.download(d_co, nco, coeffs_out))) return rc;
@@ -834,31 +846,18 @@ int anet_firi_var_dev(anet_ctx *ctx, int64_t batch, int n_bd, int max_points, in
   anet::FiriMvieArgs ma{hpoly, n_rows, ok, d_ell, d_A, L.x, L.is + (int64_t)anet::IS_DONE * ld, L.is + (int64_t)anet::IS_RET * ld,
                         d_mok, batch, ld, H};
   anet::MvieArgs ev{d_A, L.x, L.feval, L.g, L.is, batch, ld, H, P.smooth_eps, P.penalty_wt};
-  // wave-per-problem layout of the internal vectors (element i of problem b at [i + b*n]), no "still running" counter
-  anet::LbfgsArgs la{L.n, batch, L.ld, L.x, L.g, L.xp, L.gp, L.d, L.lm_s, L.lm_y, L.lm_ys, L.lm_alpha, L.pf, L.ds,
-                     L.feval, L.is, to_kernel_params(lp), nullptr, 1, L.n, nullptr, 0};
+  const anet::LbfgsArgs la = L.args(batch, lp, true);  // (one wave per corridor; no "still running" counter)
   fa.iters = iterations; ma.iters = iterations;
   for (int loop = 0; loop < P.iterations; ++loop) {
     fa.pass = loop; ma.pass = loop;
     hipLaunchKernelGGL(anet::k_firi_planes, gB, b256, 0, st, fa);
     ANET_HIP(ctx, hipGetLastError());
     if (loop == P.iterations - 1) break;
-    ANET_HIP(ctx, hipMemsetAsync(L.is, 0, sizeof(int) * anet::IS_COUNT_ * ld, st));
-    ANET_HIP(ctx, hipMemsetAsync(L.ds, 0, sizeof(double) * anet::DS_COUNT_ * ld, st));
+    ANET_HIP(ctx, L.reset(st));
     hipLaunchKernelGGL(anet::k_firi_mvie_setup, gB, b256, sizeof(double) * H * 4, st, ma);
     ANET_HIP(ctx, hipGetLastError());
-    {  // the whole MVIE optimisation in one launch, one wave per corridor; rows and optimiser state in registers when they fit
-      constexpr int kw = anet::LbfgsWaveShape<20>::kWaves;
-      const bool in_memory = anet::env_set(anet::Tuning::mvie_state_in_memory);
-      if (!in_memory && H <= 64 && lp.mem_size <= 20 && lp.past <= 64)
-        hipLaunchKernelGGL((anet::k_lbfgs_mvie_resident<20, 1>), dim3((unsigned)batch), dim3(64), 0, st, la, ev, P.mvie_max_evals);
-      else if (!in_memory && H <= 128 && lp.mem_size <= 20 && lp.past <= 64)
-        hipLaunchKernelGGL((anet::k_lbfgs_mvie_resident<20, 2>), dim3((unsigned)batch), dim3(64), 0, st, la, ev, P.mvie_max_evals);
-      else
-        hipLaunchKernelGGL(anet::k_lbfgs_mvie_persistent<20>, dim3((unsigned)((batch + kw - 1) / kw)), dim3(64u * kw), 0, st, la, ev,
-                           P.mvie_max_evals);
-      ANET_HIP(ctx, hipGetLastError());
-    }
+    launch_mvie_one_launch(la, ev, P.mvie_max_evals, st);  // the whole MVIE optimisation in one launch, one wave per corridor
+    ANET_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(anet::k_firi_mvie_finish, g64, b64, 0, st, ma);
     ANET_HIP(ctx, hipGetLastError());
   }

@@ -1,32 +1,13 @@
-// Batched L-BFGS state machine (lane-per-problem and wave-per-problem), the costMVIE objective and the
+// Batched L-BFGS with one launch per evaluation: the state machine with one lane or one wave per problem, and the
 // MINCO variable maps.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "minco_kernels.h"
+#include "lbfgs_step.h"
 #include "wave_ops.h"
 
 namespace anet {
-
-// ------------------------------------------------------------------------------------------
-// batched L-BFGS (lbfgs.hpp:276-384, 434-717) as a per-trajectory state machine
-// ------------------------------------------------------------------------------------------
-struct LbfgsP {
-  int mem_size;
-  double g_epsilon;
-  int past;
-  double delta;
-  int max_iterations, max_linesearch;
-  double min_step, max_step, f_dec_coeff, s_curv_coeff, cautious_factor, machine_prec;
-};
-enum { DS_FX = 0, DS_STEP, DS_FINIT, DS_DGTEST, DS_DSTEST, DS_MU, DS_NU, DS_SMAX, DS_COUNT_ };  // DS_SMAX: stpmax of the running line search
-enum { IS_DONE = 0, IS_RET, IS_K, IS_END, IS_BOUND, IS_COUNT, IS_BRACKT, IS_TOUCHED, IS_EVALS, IS_PHASE, IS_COUNT_ };
-enum {  // lbfgs.hpp:135-184
-  LB_CONVERGENCE = 0, LB_STOP = 1, LB_CANCELED = 2,
-  LBERR_INVALID_FUNCVAL = -1012, LBERR_MINIMUMSTEP = -1011, LBERR_MAXIMUMSTEP = -1010,
-  LBERR_MAXIMUMLINESEARCH = -1009, LBERR_MAXIMUMITERATION = -1008, LBERR_WIDTHTOOSMALL = -1007,
-  LBERR_INVALIDPARAMETERS = -1006, LBERR_INCREASEGRADIENT = -1005
-};
 
 struct LbfgsArgs {
   int n;
@@ -54,18 +35,6 @@ struct LbfgsArgs {
   // A resuming launch consumes no evaluation.
   int host_pg = 0, host_sb = 0;
 };
-enum { LB_PHASE_FIRST = 0, LB_PHASE_SEARCH = 1, LB_PHASE_AWAIT_PROGRESS = 2, LB_PHASE_AWAIT_STEPBOUND = 3 };
-__device__ __forceinline__ int read_cancel_word(const int *w) {  // system scope: written while the kernels run
-  return w ? __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0;
-}
-// x = xp + step * d as the reference computes it (lbfgs.hpp:308): the reference is built with -O3 and no -march
-// (src/planner/CMakeLists.txt:4-6), i.e. for baseline x86-64, where this is a multiply and an add -- two roundings.  The
-// trial point decides every later comparison of a line search, so the kernels round it the same way instead of fusing.
-__device__ __forceinline__ double trial_point(double step, double d, double xp) {
-#pragma clang fp contract(off)
-  const double p = step * d;
-  return xp + p;
-}
 
 __device__ __forceinline__ void store_x(const LbfgsArgs &a, int64_t b, int i, double v) {
   a.x[(int64_t)i * a.ld + b] = v;
@@ -126,48 +95,24 @@ __device__ __forceinline__ void lbfgs_update_lane(const LbfgsArgs &a, const int6
     start_ls = true;  // the direction, xp, gp, step and k are in place; the host's bound is in DS_SMAX
   } else {
     // ---- one trial of line_search_lewisoverton (lbfgs.hpp:307-383)
-    const double finit = ds[DS_FINIT * ld], dgtest = ds[DS_DGTEST * ld], dstest = ds[DS_DSTEST * ld];
-    double mu = ds[DS_MU * ld], nu = ds[DS_NU * ld];
-    const double smax = ds[DS_SMAX * ld];
-    int count = is[IS_COUNT * ld] + 1, brackt = is[IS_BRACKT * ld], touched = is[IS_TOUCHED * ld];
+    LineSearch ls;
+    ls.count = is[IS_COUNT * ld];
+    ls.brackt = is[IS_BRACKT * ld];
+    ls.touched = is[IS_TOUCHED * ld];
+    ls.finit = ds[DS_FINIT * ld];
+    ls.dgtest = ds[DS_DGTEST * ld];
+    ls.dstest = ds[DS_DSTEST * ld];
+    ls.mu = ds[DS_MU * ld];
+    ls.nu = ds[DS_NU * ld];
+    ls.smax = ds[DS_SMAX * ld];
     bool success = resume_pg;  // (parked behind a successful trial: straight to the accepted step)
     int err = 0;
-    if (resume_pg) {
-      count -= 1;
-    } else if (isinf(f) || isnan(f)) {
-      err = LBERR_INVALID_FUNCVAL;
-    } else {
-      if (f > finit + step * dgtest) {
-        nu = step;
-        brackt = 1;
-      } else {
+    if (!resume_pg)
+      err = ls_trial(P, ls, f, step, success, [&]() {
         double dg = 0.0;
         for (int i = 0; i < n; ++i) dg = __builtin_fma(g[i * ld], d[i * ld], dg);
-        if (dg < dstest)
-          mu = step;
-        else
-          success = true;
-      }
-      if (!success) {
-        if (P.max_linesearch <= count) {
-          err = LBERR_MAXIMUMLINESEARCH;
-        } else if (brackt && (nu - mu) < P.machine_prec * nu) {
-          err = LBERR_WIDTHTOOSMALL;
-        } else {
-          step = brackt ? 0.5 * (mu + nu) : step * 2.0;
-          if (step < P.min_step) {
-            err = LBERR_MINIMUMSTEP;
-          } else if (step > smax) {
-            if (touched) {
-              err = LBERR_MAXIMUMSTEP;
-            } else {
-              touched = 1;
-              step = smax;
-            }
-          }
-        }
-      }
-    }
+        return dg;
+      });
     if (err) {
       // revert to the previous point; the reported f stays the last trial's (lbfgs.hpp:570-577,713)
       for (int i = 0; i < n; ++i) {
@@ -178,86 +123,75 @@ __device__ __forceinline__ void lbfgs_update_lane(const LbfgsArgs &a, const int6
       finish = err;
     } else if (!success) {
       for (int i = 0; i < n; ++i) store_x(a, b, i, trial_point(step, d[i * ld], xp[i * ld]));
-      ds[DS_MU * ld] = mu;
-      ds[DS_NU * ld] = nu;
-      is[IS_COUNT * ld] = count;
-      is[IS_BRACKT * ld] = brackt;
-      is[IS_TOUCHED * ld] = touched;
+      ds[DS_MU * ld] = ls.mu;
+      ds[DS_NU * ld] = ls.nu;
+      is[IS_COUNT * ld] = ls.count;
+      is[IS_BRACKT * ld] = ls.brackt;
+      is[IS_TOUCHED * ld] = ls.touched;
     } else if (a.host_pg && !resume_pg) {
       // ---- accepted step, host progress callback: park (lbfgs.hpp:580-587 is the host's to run)
       fx = f;
-      is[IS_COUNT * ld] = count;
+      is[IS_COUNT * ld] = ls.count;
       is[IS_PHASE * ld] = LB_PHASE_AWAIT_PROGRESS;
     } else {
-      // ---- accepted step (lbfgs.hpp:579-709); the progress report (:580-587) comes first: non-zero cancels
+      // ---- accepted step (lbfgs.hpp:579-709)
       fx = f;
       if (resume_pg) is[IS_PHASE * ld] = LB_PHASE_SEARCH;
-      if (read_cancel_word(a.cancel)) {
-        finish = LB_CANCELED;
-      } else if (conv_test()) {
-        finish = LB_CONVERGENCE;
-      } else {
-        if (0 < P.past) {
-          if (P.past <= k) {
-            const double rate = fabs(a.pf[(int64_t)(k % P.past) * ld + b] - fx) / fmax(1.0, fabs(fx));
-            if (rate < P.delta) finish = LB_STOP;
-          }
-          if (finish == 0x7fffffff) a.pf[(int64_t)(k % P.past) * ld + b] = fx;
+      finish = stop_tests(
+          P, read_cancel_word(a.cancel), k, fx, conv_test, [&](int slot) { return a.pf[(int64_t)slot * ld + b]; },
+          [&](int slot) { a.pf[(int64_t)slot * ld + b] = fx; });
+      if (finish == 0x7fffffff) {
+        ++k;
+        int end = is[IS_END * ld], bound = is[IS_BOUND * ld];
+        double *se = a.lm_s + (int64_t)end * n * ld + b, *ye = a.lm_y + (int64_t)end * n * ld + b;
+        double ys = 0.0, yy = 0.0, ss = 0.0, gpgp = 0.0;
+        for (int i = 0; i < n; ++i) {
+          const double si = x[i * ld] - xp[i * ld], yi = g[i * ld] - gp[i * ld], gpi = gp[i * ld];
+          se[i * ld] = si;
+          ye[i * ld] = yi;
+          ys = __builtin_fma(yi, si, ys);
+          yy = __builtin_fma(yi, yi, yy);
+          ss = __builtin_fma(si, si, ss);
+          gpgp = __builtin_fma(gpi, gpi, gpgp);
+          d[i * ld] = -g[i * ld];
         }
-        if (finish == 0x7fffffff && P.max_iterations != 0 && P.max_iterations <= k) finish = LBERR_MAXIMUMITERATION;
-        if (finish == 0x7fffffff) {
-          ++k;
-          int end = is[IS_END * ld], bound = is[IS_BOUND * ld];
-          double *se = a.lm_s + (int64_t)end * n * ld + b, *ye = a.lm_y + (int64_t)end * n * ld + b;
-          double ys = 0.0, yy = 0.0, ss = 0.0, gpgp = 0.0;
-          for (int i = 0; i < n; ++i) {
-            const double si = x[i * ld] - xp[i * ld], yi = g[i * ld] - gp[i * ld], gpi = gp[i * ld];
-            se[i * ld] = si;
-            ye[i * ld] = yi;
-            ys = __builtin_fma(yi, si, ys);
-            yy = __builtin_fma(yi, yi, yy);
-            ss = __builtin_fma(si, si, ss);
-            gpgp = __builtin_fma(gpi, gpi, gpgp);
-            d[i * ld] = -g[i * ld];
+        a.lm_ys[(int64_t)end * ld + b] = ys;
+        const double cau = ss * sqrt(gpgp) * P.cautious_factor;
+        if (ys > cau) {
+          ++bound;
+          bound = m < bound ? m : bound;
+          end = (end + 1) % m;
+          int j = end;
+          for (int it = 0; it < bound; ++it) {
+            j = (j + m - 1) % m;
+            const double *sj = a.lm_s + (int64_t)j * n * ld + b, *yj = a.lm_y + (int64_t)j * n * ld + b;
+            double sd = 0.0;
+            for (int i = 0; i < n; ++i) sd = __builtin_fma(sj[i * ld], d[i * ld], sd);
+            const double al = sd / a.lm_ys[(int64_t)j * ld + b];
+            a.lm_alpha[(int64_t)j * ld + b] = al;
+            for (int i = 0; i < n; ++i) d[i * ld] = __builtin_fma(-al, yj[i * ld], d[i * ld]);
           }
-          a.lm_ys[(int64_t)end * ld + b] = ys;
-          const double cau = ss * sqrt(gpgp) * P.cautious_factor;
-          if (ys > cau) {
-            ++bound;
-            bound = m < bound ? m : bound;
-            end = (end + 1) % m;
-            int j = end;
-            for (int it = 0; it < bound; ++it) {
-              j = (j + m - 1) % m;
-              const double *sj = a.lm_s + (int64_t)j * n * ld + b, *yj = a.lm_y + (int64_t)j * n * ld + b;
-              double sd = 0.0;
-              for (int i = 0; i < n; ++i) sd = __builtin_fma(sj[i * ld], d[i * ld], sd);
-              const double al = sd / a.lm_ys[(int64_t)j * ld + b];
-              a.lm_alpha[(int64_t)j * ld + b] = al;
-              for (int i = 0; i < n; ++i) d[i * ld] = __builtin_fma(-al, yj[i * ld], d[i * ld]);
-            }
-            const double sc = ys / yy;
-            for (int i = 0; i < n; ++i) d[i * ld] *= sc;
-            for (int it = 0; it < bound; ++it) {
-              const double *sj = a.lm_s + (int64_t)j * n * ld + b, *yj = a.lm_y + (int64_t)j * n * ld + b;
-              double yd = 0.0;
-              for (int i = 0; i < n; ++i) yd = __builtin_fma(yj[i * ld], d[i * ld], yd);
-              const double beta = yd / a.lm_ys[(int64_t)j * ld + b];
-              const double cf = a.lm_alpha[(int64_t)j * ld + b] - beta;
-              for (int i = 0; i < n; ++i) d[i * ld] = __builtin_fma(cf, sj[i * ld], d[i * ld]);
-              j = (j + 1) % m;
-            }
+          const double sc = ys / yy;
+          for (int i = 0; i < n; ++i) d[i * ld] *= sc;
+          for (int it = 0; it < bound; ++it) {
+            const double *sj = a.lm_s + (int64_t)j * n * ld + b, *yj = a.lm_y + (int64_t)j * n * ld + b;
+            double yd = 0.0;
+            for (int i = 0; i < n; ++i) yd = __builtin_fma(yj[i * ld], d[i * ld], yd);
+            const double beta = yd / a.lm_ys[(int64_t)j * ld + b];
+            const double cf = a.lm_alpha[(int64_t)j * ld + b] - beta;
+            for (int i = 0; i < n; ++i) d[i * ld] = __builtin_fma(cf, sj[i * ld], d[i * ld]);
+            j = (j + 1) % m;
           }
-          is[IS_END * ld] = end;
-          is[IS_BOUND * ld] = bound;
-          step = 1.0;
-          start_ls = true;
         }
+        is[IS_END * ld] = end;
+        is[IS_BOUND * ld] = bound;
+        step = 1.0;
+        start_ls = true;
       }
     }
   }
   if (start_ls) {
-    // ---- entry of line_search_lewisoverton (lbfgs.hpp:287-305) for the new direction
+    // ---- lbfgs.hpp:557-565 and the entry of line_search_lewisoverton (lbfgs.hpp:287-305) for the new direction
     double dginit = 0.0;
     for (int i = 0; i < n; ++i) {
       const double xi = x[i * ld], gi = g[i * ld];
@@ -265,43 +199,36 @@ __device__ __forceinline__ void lbfgs_update_lane(const LbfgsArgs &a, const int6
       gp[i * ld] = gi;
       dginit = __builtin_fma(gi, d[i * ld], dginit);
     }
-    double smax = P.max_step;
-    bool parked = false;
     if (a.host_sb && !resume_sb) {  // the host's proc_stepbound(xp, d) comes first: park with xp, gp, d in place
-      is[IS_PHASE * ld] = LB_PHASE_AWAIT_STEPBOUND;
-      parked = true;
-    } else if (a.host_sb) {        // lbfgs.hpp:557-565 with the host's value
-      const double bnd = ds[DS_SMAX * ld];
-      smax = bnd < P.max_step ? bnd : P.max_step;
-      step = step < smax ? step : 0.5 * smax;
-      is[IS_PHASE * ld] = LB_PHASE_SEARCH;
-    } else if (a.sb_on) {  // lbfgs.hpp:557-565: step_max = min(proc_stepbound(xp, d), max_step); step = step < step_max ? step : step_max / 2
-      double worst = 0.0;
-      for (int i = a.sb_lo; i < n; ++i) {
-        const double di = d[i * ld], room = x[i * ld] - a.sb_xmin;
-        if (di < 0.0) worst = fmax(worst, -di / (room > 1e-300 ? room : 1e-300));
-      }
-      const double bnd = worst > 0.0 ? 1.0 / worst : INFINITY;
-      smax = bnd < P.max_step ? bnd : P.max_step;
-      step = step < smax ? step : 0.5 * smax;
-    }
-    if (!parked) ds[DS_SMAX * ld] = smax;
-    if (parked) {
-      // (nothing more until the host has answered)
-    } else if (!(step > 0.0)) {
-      finish = LBERR_INVALIDPARAMETERS;
-    } else if (0.0 < dginit) {
-      finish = LBERR_INCREASEGRADIENT;
+      is[IS_PHASE * ld] = LB_PHASE_AWAIT_STEPBOUND;  // (nothing more until the host has answered)
     } else {
-      ds[DS_FINIT * ld] = fx;
-      ds[DS_DGTEST * ld] = P.f_dec_coeff * dginit;
-      ds[DS_DSTEST * ld] = P.s_curv_coeff * dginit;
-      ds[DS_MU * ld] = 0.0;
-      ds[DS_NU * ld] = smax;
-      is[IS_COUNT * ld] = 0;
-      is[IS_BRACKT * ld] = 0;
-      is[IS_TOUCHED * ld] = 0;
-      for (int i = 0; i < n; ++i) store_x(a, b, i, trial_point(step, d[i * ld], xp[i * ld]));
+      if (a.host_sb) is[IS_PHASE * ld] = LB_PHASE_SEARCH;  // resumed: the host's value is in DS_SMAX
+      LineSearch ls;
+      ls.smax = P.max_step;
+      if (a.host_sb) {  // lbfgs.hpp:557-565 with the host's value
+        ls_bound_step(P, ls, step, ds[DS_SMAX * ld]);
+      } else if (a.sb_on) {
+        double worst = 0.0;
+        for (int i = a.sb_lo; i < n; ++i) {
+          const double di = d[i * ld];
+          if (di < 0.0) worst = fmax(worst, step_bound_ratio(di, x[i * ld], a.sb_xmin));
+        }
+        ls_bound_step(P, ls, step, step_bound_of(worst));
+      }
+      finish = ls_entry_check(step, dginit);
+      if (finish == 0x7fffffff) {
+        ls_fresh(P, ls, fx, dginit);
+        ds[DS_FINIT * ld] = ls.finit;
+        ds[DS_DGTEST * ld] = ls.dgtest;
+        ds[DS_DSTEST * ld] = ls.dstest;
+        ds[DS_MU * ld] = ls.mu;
+        ds[DS_NU * ld] = ls.nu;
+        is[IS_COUNT * ld] = ls.count;
+        is[IS_BRACKT * ld] = ls.brackt;
+        is[IS_TOUCHED * ld] = ls.touched;
+        for (int i = 0; i < n; ++i) store_x(a, b, i, trial_point(step, d[i * ld], xp[i * ld]));
+      }
+      ds[DS_SMAX * ld] = ls.smax;
     }
   }
   ds[DS_FX * ld] = fx;
@@ -315,38 +242,9 @@ __device__ __forceinline__ void lbfgs_update_lane(const LbfgsArgs &a, const int6
   }
 }
 
-
 __global__ void __launch_bounds__(64) k_lbfgs_update(LbfgsArgs a) {
   const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
   if (b < a.B) lbfgs_update_lane(a, b);
-}
-
-// a value every lane holds identically (loaded from a wave-uniform address) -> SGPR pair
-__device__ __forceinline__ double uniform_f64(double v) {
-  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)),
-                          __builtin_amdgcn_readfirstlane(__double2loint(v)));
-}
-// Two problems per wave (32 lanes each): the same scans, chained over the two rows of a half only; each half then
-// reads its total from its own last lane.  Needs the lanes of a HALF to be active together, not the whole wave.
-__device__ __forceinline__ double half_pick(double v) {
-  const double lo = last_lane<31>(v), hi = last_lane<63>(v);
-  return (threadIdx.x & 32) ? hi : lo;
-}
-__device__ __forceinline__ double half_sum(double v) {
-  v += dpp_f64<0x111>(v);
-  v += dpp_f64<0x112>(v);
-  v += dpp_f64<0x114>(v);
-  v += dpp_f64<0x118>(v);
-  v += dpp_f64<0x142, 0xa>(v);
-  return half_pick(v);
-}
-__device__ __forceinline__ double half_max_nonneg(double v) {
-  v = fmax(v, dpp_f64<0x111>(v));
-  v = fmax(v, dpp_f64<0x112>(v));
-  v = fmax(v, dpp_f64<0x114>(v));
-  v = fmax(v, dpp_f64<0x118>(v));
-  v = fmax(v, dpp_f64<0x142, 0xa>(v));
-  return half_pick(v);
 }
 
 // Same state machine, ONE WAVE per problem: the n <= 128 variables are spread over the 64 lanes (two
@@ -385,6 +283,10 @@ struct WaveHistory {
 // HALF: the wave carries TWO problems of at most 32 variables, `lane` is the lane within the half (0..31) and `b`
 // differs between the halves: nothing is wave-uniform any more (state in vector registers, branches by exec mask),
 // every reduction runs in both halves at once.  Half the instruction issue per problem -- what bounds the kernel.
+// The step's scalar logic is written out here, not taken from lbfgs_step.h as in the other two forms: with the line search's
+// nine scalars in a LineSearch -- all three shared pieces in place or not -- k_lbfgs_update_wave<8, 1, true> measured 0.671 ms
+// per lockstep evaluation step of 131072 problems against 0.660 ms (spread 0.001) with them as locals.  Keep it in step with
+// ls_trial / ls_bound_step / ls_entry_check / ls_fresh / stop_tests.
 template <int LBFGS_WAVE_MREG, int NV = 2, bool CARRY = false, int RL = 63, bool HALF = false>
 __device__ __forceinline__ void lbfgs_update_wave_body(const LbfgsArgs &a, const int64_t b, const int lane,
                                                        WaveHistory<(LBFGS_WAVE_MREG > 0 ? LBFGS_WAVE_MREG : 1), NV> &H) {
@@ -760,156 +662,6 @@ k_lbfgs_update_wave(LbfgsArgs a) {
   if (b >= a.B) return;  // whole waves (halves) only: the reductions need all their lanes
   WaveHistory<(LBFGS_WAVE_MREG > 0 ? LBFGS_WAVE_MREG : 1), NV> H;
   lbfgs_update_wave_body<LBFGS_WAVE_MREG, NV, false, 63, HALF>(a, b, HALF ? (threadIdx.x & 31) : (threadIdx.x & 63), H);
-}
-
-// firi::costMVIE (gcopter/firi.hpp:86-157): x = [p, rtd, cde], A is M x 3 column-major per problem
-// (field k*M + r), the reference's optData packing (firi.hpp:186-200).
-struct MvieArgs {
-  const double *A, *x;
-  double *f, *g;
-  const int *done;
-  int64_t B, ld;
-  int M;
-  double eps, wt;
-};
-__device__ __forceinline__ void mvie_eval_lane(const MvieArgs &a, const int64_t b) {
-  if (a.done && a.done[b]) return;
-  const int64_t ld = a.ld;
-  const double *x = a.x + b;
-  double p[3], rtd[3], cde[3];
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    p[q] = x[q * ld];
-    rtd[q] = x[(3 + q) * ld];
-    cde[q] = x[(6 + q) * ld];
-  }
-  const double L00 = rtd[0] * rtd[0] + 2.220446049250313e-16, L11 = rtd[1] * rtd[1] + 2.220446049250313e-16,
-               L22 = rtd[2] * rtd[2] + 2.220446049250313e-16;
-  const double L10 = cde[0], L21 = cde[1], L20 = cde[2];
-  double cost = 0.0, gdp[3] = {0, 0, 0}, gdr[3] = {0, 0, 0}, gdc[3] = {0, 0, 0};
-  const double inv_mu = 1.0 / a.eps;
-  for (int r = 0; r < a.M; ++r) {
-    const double a0 = a.A[(int64_t)r * ld + b], a1 = a.A[(int64_t)(a.M + r) * ld + b],
-                 a2 = a.A[(int64_t)(2 * a.M + r) * ld + b];
-    const double al0 = a0 * L00 + a1 * L10 + a2 * L20, al1 = a1 * L11 + a2 * L21, al2 = a2 * L22;
-    const double nrm = sqrt(al0 * al0 + al1 * al1 + al2 * al2);
-    const double viol = nrm + (a0 * p[0] + a1 * p[1] + a2 * p[2]) - 1.0;
-    if (viol >= 0.0) {
-      double c, dc;
-      smoothed_l1(a.eps, inv_mu, viol, c, dc);
-      const double inv = 1.0 / nrm;
-      const double adj0 = al0 * inv, adj1 = al1 * inv, adj2 = al2 * inv;
-      const double v0 = dc * a0, v1 = dc * a1, v2 = dc * a2;
-      cost += c;
-      gdp[0] += v0; gdp[1] += v1; gdp[2] += v2;
-      gdr[0] += adj0 * v0; gdr[1] += adj1 * v1; gdr[2] += adj2 * v2;
-      gdc[0] += adj0 * v1;
-      gdc[1] += adj1 * v2;
-      gdc[2] += adj0 * v2;
-    }
-  }
-  cost *= a.wt;
-  cost -= log(L00) + log(L11) + log(L22);
-  const double Ld[3] = {L00, L11, L22};
-  double *g = a.g + b;
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    g[q * ld] = gdp[q] * a.wt;
-    g[(3 + q) * ld] = (gdr[q] * a.wt - 1.0 / Ld[q]) * 2.0 * rtd[q];
-    g[(6 + q) * ld] = gdc[q] * a.wt;
-  }
-  a.f[b] = cost;
-}
-__global__ void __launch_bounds__(64) k_mvie_eval(MvieArgs a) {
-  const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (b < a.B) mvie_eval_lane(a, b);
-}
-
-// costMVIE with one WAVE per problem: the rows of A are spread over the lanes, the ten sums (cost, nine gradient
-// parts) are wave reductions.  Same quantities as mvie_eval_lane, summed in a different order.
-__device__ __forceinline__ void mvie_eval_wave(const MvieArgs &a, const int64_t b, const int lane) {
-  const int64_t ld = a.ld;
-  const double *x = a.x + b;
-  double p[3], rtd[3], cde[3];
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    p[q] = x[q * ld];
-    rtd[q] = x[(3 + q) * ld];
-    cde[q] = x[(6 + q) * ld];
-  }
-  const double L00 = rtd[0] * rtd[0] + 2.220446049250313e-16, L11 = rtd[1] * rtd[1] + 2.220446049250313e-16,
-               L22 = rtd[2] * rtd[2] + 2.220446049250313e-16;
-  const double L10 = cde[0], L21 = cde[1], L20 = cde[2];
-  double cost = 0.0, gdp[3] = {0, 0, 0}, gdr[3] = {0, 0, 0}, gdc[3] = {0, 0, 0};
-  const double inv_mu = 1.0 / a.eps;
-  for (int r = lane; r < a.M; r += 64) {
-    const double a0 = a.A[(int64_t)r * ld + b], a1 = a.A[(int64_t)(a.M + r) * ld + b],
-                 a2 = a.A[(int64_t)(2 * a.M + r) * ld + b];
-    const double al0 = a0 * L00 + a1 * L10 + a2 * L20, al1 = a1 * L11 + a2 * L21, al2 = a2 * L22;
-    const double nrm = sqrt(al0 * al0 + al1 * al1 + al2 * al2);
-    const double viol = nrm + (a0 * p[0] + a1 * p[1] + a2 * p[2]) - 1.0;
-    if (viol >= 0.0) {
-      double c, dc;
-      smoothed_l1(a.eps, inv_mu, viol, c, dc);
-      const double inv = 1.0 / nrm;
-      const double adj0 = al0 * inv, adj1 = al1 * inv, adj2 = al2 * inv;
-      const double v0 = dc * a0, v1 = dc * a1, v2 = dc * a2;
-      cost += c;
-      gdp[0] += v0; gdp[1] += v1; gdp[2] += v2;
-      gdr[0] += adj0 * v0; gdr[1] += adj1 * v1; gdr[2] += adj2 * v2;
-      gdc[0] += adj0 * v1;
-      gdc[1] += adj1 * v2;
-      gdc[2] += adj0 * v2;
-    }
-  }
-  cost = wave_sum(cost);
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    gdp[q] = wave_sum(gdp[q]);
-    gdr[q] = wave_sum(gdr[q]);
-    gdc[q] = wave_sum(gdc[q]);
-  }
-  cost *= a.wt;
-  cost -= log(L00) + log(L11) + log(L22);
-  const double Ld[3] = {L00, L11, L22};
-  if (lane == 0) {
-    double *g = a.g + b;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      g[q * ld] = gdp[q] * a.wt;
-      g[(3 + q) * ld] = (gdr[q] * a.wt - 1.0 / Ld[q]) * 2.0 * rtd[q];
-      g[(6 + q) * ld] = gdc[q] * a.wt;
-    }
-    a.f[b] = cost;
-  }
-}
-
-// A whole MVIE optimisation in ONE launch: one wave per problem loops evaluation + L-BFGS update (the same
-// update body as k_lbfgs_update_wave, state in the same arrays).  The launch-per-evaluation driver spends a
-// corridor search of a handful of segments almost entirely on launch latency (hundreds of evaluations of a
-// 9-variable problem); here an evaluation costs a few memory round trips.  The fences order the cross-lane
-// traffic through global memory inside the wave (workgroup scope: the lanes share one L1).
-template <int LBFGS_WAVE_MREG>
-__global__ void __launch_bounds__(64 * LbfgsWaveShape<LBFGS_WAVE_MREG>::kWaves)
-k_lbfgs_mvie_persistent(LbfgsArgs la, MvieArgs ma, int max_evals) {
-  const int64_t b = (int64_t)blockIdx.x * LbfgsWaveShape<LBFGS_WAVE_MREG>::kWaves + (threadIdx.x >> 6);
-  if (b >= la.B) return;
-  const int lane = threadIdx.x & 63;
-  const int *done = la.is + (int64_t)IS_DONE * la.ld + b;
-  // When mem_size fits, the history stays in registers across the iterations: the first one fills it from memory
-  // as the per-launch kernel does (nothing to read in a fresh run), the later ones carry it.
-  WaveHistory<(LBFGS_WAVE_MREG > 0 ? LBFGS_WAVE_MREG : 1), 1> H;
-  H.clear();
-  const bool carry = LBFGS_WAVE_MREG > 0 && la.p.mem_size <= LBFGS_WAVE_MREG;
-  for (int e = 0; e < max_evals; ++e) {
-    if (__builtin_amdgcn_readfirstlane(*(volatile const int *)done)) break;
-    mvie_eval_wave(ma, b, lane);
-    __threadfence_block();
-    // nine variables: one per lane
-    if (carry && e > 0) lbfgs_update_wave_body<LBFGS_WAVE_MREG, 1, true, 15>(la, b, lane, H);
-    else lbfgs_update_wave_body<LBFGS_WAVE_MREG, 1, false, 15>(la, b, lane, H);
-    __threadfence_block();
-  }
 }
 
 struct MapArgs {

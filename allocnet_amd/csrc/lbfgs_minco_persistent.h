@@ -16,7 +16,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "lbfgs_kernels.h"
+#include "minco_kernels.h"
+#include "lbfgs_resident.h"
 
 namespace anet {
 
@@ -61,8 +62,6 @@ struct PersistArgs {
 #define PERSIST_TICK_DECL do {} while (0)
 #endif
 
-constexpr int kPersistContLaneFields = 22, kPersistContDoubles = (kPersistContLaneFields + 1) * 64;
-
 template <int S, int NB>
 struct PersistLds {
   static constexpr int m = S - 1, D = 2 * S, nl = m * (m - 1) / 2;
@@ -98,18 +97,6 @@ constexpr size_t persist_lds_fixed_bytes() { return (sizeof(PersistLds<S, NB>) +
 // corridor rows of piece i start at i * (4 M4 + 4) doubles, M4 = M rounded up to a multiple of four with zero rows
 // (a zero row is never violated); the pad of four doubles spreads the pieces over the LDS banks
 inline size_t persist_lds_row_doubles(int N, int M) { return (size_t)N * (4 * (size_t)((M + 3) & ~3) + 4); }
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_add(double v) { return v + dpp_f64<CTRL>(v); }
-// sum over the G adjacent lanes of a group (G = 4, 8, 16; every lane of the group ends with the total)
-template <int G>
-__device__ __forceinline__ double group_sum(double v) {
-  v = dpp_add<0xB1>(v);                          // quad_perm [1,0,3,2]
-  v = dpp_add<0x4E>(v);                          // quad_perm [2,3,0,1]
-  if constexpr (G >= 8) v = dpp_add<0x141>(v);   // row_half_mirror
-  if constexpr (G >= 16) v = dpp_add<0x140>(v);  // row_mirror
-  return v;
-}
 
 template <int S>
 struct BlkOps {
@@ -184,323 +171,6 @@ __device__ __forceinline__ void rhs_primal_node_rt(int k, int N, int np, double 
 #pragma unroll
     for (int l = 0; l < m; ++l)
       if (l < np) y[l] = (k == 0) ? hv[l] : tv[l];
-  }
-}
-
-// The register-resident L-BFGS of one problem: lbfgs_update_wave_body (one variable per lane, history carried)
-// without its loads and stores.  pf: lane j holds pf[j] of the past-f ring.
-// LAST: the highest lane that can hold a non-zero component (63: any n <= 64; 15: n <= 16, reductions stop after one row).
-// lbfgs_optimize's proc_stepbound (lbfgs.hpp:221-224, 557-565) as a built-in: the largest step along d that keeps the variables
-// of lanes [lo, hi) at or above xmin -- for the MINCO objective the duration variables tau and xmin = backward_T(minimum
-// duration), so that no line search ever leaves T >= T_min.  on = 0: no bound (step_max = max_step, as with a NULL callback).
-struct StepBound {
-  int on, lo, hi;
-  double xmin;
-};
-
-template <int MR, int LAST = 63>
-struct LbfgsResident {
-  double x, g, d, xp, gp;
-  double smax;  // stpmax of the current line search: min(step bound, max_step)
-  double hs[MR], hy[MR], hys[MR];  // hys: 1 / (y.s) of the slot
-  double fx, step, finit, dgtest, dstest, mu, nu, pf;
-  int k, bound, count, brackt, touched, evals, phase;
-
-  __device__ __forceinline__ void init(double x0) {
-    x = x0;
-    g = d = xp = gp = 0.0;
-#pragma unroll
-    for (int it = 0; it < MR; ++it) {
-      hs[it] = hy[it] = 0.0;
-      hys[it] = 1.0;
-    }
-    fx = step = finit = dgtest = dstest = mu = nu = pf = smax = 0.0;
-    k = bound = count = brackt = touched = evals = phase = 0;
-  }
-  // the whole state to / from global memory ([field][lane], then 64 wave-uniform values): what a second launch needs to go on
-  // exactly where this one stopped (PersistArgs::park / resume)
-  __device__ __forceinline__ void park(double *c, const int lane, const double f_half) const {
-    static_assert(MR <= 8, "layout of the parked state");
-    double *pl = c + lane;
-    pl[0 * 64] = x; pl[1 * 64] = g; pl[2 * 64] = d; pl[3 * 64] = xp; pl[4 * 64] = gp; pl[5 * 64] = pf;
-#pragma unroll
-    for (int it = 0; it < MR; ++it) {
-      pl[(6 + it) * 64] = hs[it];
-      pl[(14 + it) * 64] = hy[it];
-    }
-    const double gn2 = dot(gp, gp);
-    if (lane == 0) {
-      double *u = c + 22 * 64;
-#pragma unroll
-      for (int it = 0; it < MR; ++it) u[it] = hys[it];
-      u[8] = fx; u[9] = step; u[10] = finit; u[11] = dgtest; u[12] = dstest; u[13] = mu; u[14] = nu; u[15] = smax;
-      u[16] = (double)k; u[17] = (double)bound; u[18] = (double)count; u[19] = (double)brackt; u[20] = (double)touched;
-      u[21] = (double)evals; u[22] = (double)phase;
-      u[23] = f_half;  // (for the order of the second launch only)
-      u[24] = gn2;
-    }
-  }
-  __device__ __forceinline__ void unpark(const double *c, const int lane) {
-    const double *pl = c + lane;
-    x = pl[0 * 64]; g = pl[1 * 64]; d = pl[2 * 64]; xp = pl[3 * 64]; gp = pl[4 * 64]; pf = pl[5 * 64];
-#pragma unroll
-    for (int it = 0; it < MR; ++it) {
-      hs[it] = pl[(6 + it) * 64];
-      hy[it] = pl[(14 + it) * 64];
-    }
-    const double *u = c + 22 * 64;
-#pragma unroll
-    for (int it = 0; it < MR; ++it) hys[it] = u[it];
-    fx = u[8]; step = u[9]; finit = u[10]; dgtest = u[11]; dstest = u[12]; mu = u[13]; nu = u[14]; smax = u[15];
-    k = (int)u[16]; bound = (int)u[17]; count = (int)u[18]; brackt = (int)u[19]; touched = (int)u[20];
-    evals = (int)u[21]; phase = (int)u[22];
-  }
-  __device__ __forceinline__ static double dot(double u, double v) { return wave_sum<LAST>(u * v); }
-  // |g|_inf / max(1, |x|_inf) < g_epsilon (lbfgs.hpp:520-524, 592-596), the quotient cleared
-  // (g_epsilon = 0, the setting of the reference's only call site: a norm is never below zero, the two reductions are skipped)
-  __device__ __forceinline__ bool conv_test(const LbfgsP &P) const {
-    if (!(P.g_epsilon > 0.0)) return false;
-    return wave_max_nonneg<LAST>(fabs(g)) < P.g_epsilon * fmax(1.0, wave_max_nonneg<LAST>(fabs(x)));
-  }
-  // consumes f = objective at x (gradient already in g); leaves the next point in x.  Returns the lbfgs.hpp
-  // return code when the problem stops, 0x7fffffff while it runs.
-  __device__ __forceinline__ int update(const LbfgsP &P, const int lane, const double f, const StepBound sb = StepBound{0, 0, 0, 0.0},
-                                        const int cancel = 0) {
-    const int m = P.mem_size;
-    ++evals;
-    bool start_ls = false;
-    int finish = 0x7fffffff;
-    if (phase == 0) {
-      fx = f;
-      pf = (lane == 0) ? fx : pf;
-      d = -g;
-      const double dd = dot(g, g);
-      if (conv_test(P)) {
-        finish = LB_CONVERGENCE;
-      } else {
-        step = 1.0 / sqrt(dd);
-        k = 1;
-        bound = 0;
-        phase = 1;
-        start_ls = true;
-      }
-    } else {
-      ++count;
-      bool success = false;
-      int err = 0;
-      if (isinf(f) || isnan(f)) {
-        err = LBERR_INVALID_FUNCVAL;
-      } else {
-        if (f > finit + step * dgtest) {
-          nu = step;
-          brackt = 1;
-        } else {
-          const double dg = dot(g, d);
-          if (dg < dstest) mu = step;
-          else success = true;
-        }
-        if (!success) {
-          if (P.max_linesearch <= count) {
-            err = LBERR_MAXIMUMLINESEARCH;
-          } else if (brackt && (nu - mu) < P.machine_prec * nu) {
-            err = LBERR_WIDTHTOOSMALL;
-          } else {
-            step = brackt ? 0.5 * (mu + nu) : step * 2.0;
-            if (step < P.min_step) {
-              err = LBERR_MINIMUMSTEP;
-            } else if (step > smax) {
-              if (touched) {
-                err = LBERR_MAXIMUMSTEP;
-              } else {
-                touched = 1;
-                step = smax;
-              }
-            }
-          }
-        }
-      }
-      if (err) {  // revert; the reported f stays the last trial's (lbfgs.hpp:570-577,713)
-        x = xp;
-        g = gp;
-        fx = f;
-        finish = err;
-      } else if (!success) {
-        x = trial_point(step, d, xp);
-      } else {
-        fx = f;
-        if (cancel) {  // lbfgs.hpp:580-587: the progress report comes first after a line search; non-zero cancels
-          finish = LB_CANCELED;
-        } else if (conv_test(P)) {
-          finish = LB_CONVERGENCE;
-        } else {
-          if (0 < P.past) {
-            const int slot = k % P.past;
-            if (P.past <= k) {
-              const double pf_old = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(pf), slot),
-                                                     __builtin_amdgcn_readlane(__double2loint(pf), slot));
-              const double rate = fabs(pf_old - fx) / fmax(1.0, fabs(fx));
-              if (rate < P.delta) finish = LB_STOP;
-            }
-            if (finish == 0x7fffffff) pf = (lane == slot) ? fx : pf;
-          }
-          if (finish == 0x7fffffff && P.max_iterations != 0 && P.max_iterations <= k) finish = LBERR_MAXIMUMITERATION;
-          if (finish == 0x7fffffff) {
-            ++k;
-            const double sreg = x - xp, yreg = g - gp;
-            double dv = -g;
-            const double ys = dot(yreg, sreg), yy = dot(yreg, yreg), ss = dot(sreg, sreg), gpgp = dot(gp, gp);
-            const double cau = ss * sqrt(gpgp) * P.cautious_factor;
-            if (ys > cau) {
-              ++bound;
-              bound = m < bound ? m : bound;
-              hs[0] = sreg;
-              hy[0] = yreg;
-              hys[0] = 1.0 / ys;  // one division per stored pair instead of two per slot and iteration
-              double alpha[MR];
-#pragma unroll
-              for (int it = 0; it < MR; ++it) {
-                alpha[it] = 0.0;
-                if (it < bound) {
-                  alpha[it] = dot(hs[it], dv) * hys[it];
-                  dv = __builtin_fma(-alpha[it], hy[it], dv);
-                }
-              }
-              dv *= ys / yy;
-#pragma unroll
-              for (int it = MR - 1; it >= 0; --it) {
-                if (it < bound) {
-                  const double cf = alpha[it] - dot(hy[it], dv) * hys[it];
-                  dv = __builtin_fma(cf, hs[it], dv);
-                }
-              }
-#pragma unroll
-              for (int it = MR - 1; it > 0; --it) {  // the stored pair is one slot behind the next new pair
-                hs[it] = hs[it - 1];
-                hy[it] = hy[it - 1];
-                hys[it] = hys[it - 1];
-              }
-            }
-            d = dv;
-            step = 1.0;
-            start_ls = true;
-          }
-        }
-      }
-    }
-    if (start_ls) {  // lbfgs.hpp:553-565, then the entry of line_search_lewisoverton (lbfgs.hpp:287-305)
-      xp = x;
-      gp = g;
-      smax = P.max_step;
-      if (sb.on) {  // step_max = proc_stepbound(xp, d); step_max = min(step_max, max_step); step = step < step_max ? step : step_max / 2
-        const bool mine = lane >= sb.lo && lane < sb.hi && d < 0.0;
-        const double room = x - sb.xmin;
-        const double q = mine ? -d / (room > 1e-300 ? room : 1e-300) : 0.0;
-        const double worst = wave_max_nonneg<LAST>(q);
-        const double bnd = worst > 0.0 ? 1.0 / worst : INFINITY;
-        smax = bnd < P.max_step ? bnd : P.max_step;
-        step = step < smax ? step : 0.5 * smax;
-      }
-      const double dginit = dot(g, d);
-      if (!(step > 0.0)) {
-        finish = LBERR_INVALIDPARAMETERS;
-      } else if (0.0 < dginit) {
-        finish = LBERR_INCREASEGRADIENT;
-      } else {
-        finit = fx;
-        dgtest = P.f_dec_coeff * dginit;
-        dstest = P.s_curv_coeff * dginit;
-        mu = 0.0;
-        nu = smax;
-        count = 0;
-        brackt = 0;
-        touched = 0;
-        x = trial_point(step, d, x);
-      }
-    }
-    return finish;
-  }
-};
-
-// firi::maxVolInsEllipsoid's optimisation (firi.hpp:207-227) in one launch with NOTHING in memory between the iterations:
-// one wave per polytope, the rows of A in registers (lane = row, RG groups of 64), the nine variables and the L-BFGS
-// state in LbfgsResident (variable = lane), costMVIE (firi.hpp:86-157) as ten wave sums over the rows.  The variant with
-// the state in memory (k_lbfgs_mvie_persistent: x, g, f and the optimiser state through L1 / L2 every iteration) spent
-// about half of an iteration on those round trips.  Same arithmetic as mvie_eval_wave + lbfgs_update_wave_body.
-template <int MR, int RG>
-__global__ void __launch_bounds__(64) k_lbfgs_mvie_resident(LbfgsArgs la, MvieArgs ma, int max_evals) {
-  const int64_t b = blockIdx.x, ld = la.ld;
-  const int lane = threadIdx.x;
-  if (la.is[(int64_t)IS_DONE * ld + b]) return;  // (corridors FIRI's set-up found empty)
-  double a0[RG], a1[RG], a2[RG];
-#pragma unroll
-  for (int g = 0; g < RG; ++g) {
-    const int r = lane + 64 * g;
-    const bool v = r < ma.M;
-    a0[g] = v ? ma.A[(int64_t)r * ld + b] : 0.0;
-    a1[g] = v ? ma.A[(int64_t)(ma.M + r) * ld + b] : 0.0;
-    a2[g] = v ? ma.A[(int64_t)(2 * ma.M + r) * ld + b] : 0.0;
-  }
-  LbfgsResident<MR, 15> st;
-  st.init(lane < 9 ? la.x[(int64_t)lane * ld + b] : 0.0);
-  const double inv_mu = 1.0 / ma.eps;
-  int finish = 0x7fffffff;
-#pragma unroll 1
-  for (int e = 0; e < max_evals; ++e) {
-    double xv[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q)
-      xv[q] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(st.x), q), __builtin_amdgcn_readlane(__double2loint(st.x), q));
-    const double L00 = xv[3] * xv[3] + 2.220446049250313e-16, L11 = xv[4] * xv[4] + 2.220446049250313e-16,
-                 L22 = xv[5] * xv[5] + 2.220446049250313e-16;
-    const double L10 = xv[6], L21 = xv[7], L20 = xv[8];
-    double cost = 0.0, gdp[3] = {0, 0, 0}, gdr[3] = {0, 0, 0}, gdc[3] = {0, 0, 0};
-#pragma unroll
-    for (int g = 0; g < RG; ++g) {
-      const double al0 = a0[g] * L00 + a1[g] * L10 + a2[g] * L20, al1 = a1[g] * L11 + a2[g] * L21, al2 = a2[g] * L22;
-      const double nrm = sqrt(al0 * al0 + al1 * al1 + al2 * al2);
-      const double viol = nrm + (a0[g] * xv[0] + a1[g] * xv[1] + a2[g] * xv[2]) - 1.0;
-      if (viol >= 0.0) {
-        double c, dc;
-        smoothed_l1(ma.eps, inv_mu, viol, c, dc);
-        const double inv = fast_rcp(nrm);  // (v_rcp_f64 + two Newton steps: 5 instructions where the IEEE division takes ~30)
-        const double adj0 = al0 * inv, adj1 = al1 * inv, adj2 = al2 * inv;
-        const double v0 = dc * a0[g], v1 = dc * a1[g], v2 = dc * a2[g];
-        cost += c;
-        gdp[0] += v0; gdp[1] += v1; gdp[2] += v2;
-        gdr[0] += adj0 * v0; gdr[1] += adj1 * v1; gdr[2] += adj2 * v2;
-        gdc[0] += adj0 * v1;
-        gdc[1] += adj1 * v2;
-        gdc[2] += adj0 * v2;
-      }
-    }
-    cost = wave_sum(cost);
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      gdp[q] = wave_sum(gdp[q]);
-      gdr[q] = wave_sum(gdr[q]);
-      gdc[q] = wave_sum(gdc[q]);
-    }
-    cost *= ma.wt;
-    cost -= log(L00 * L11 * L22);  // (one logarithm instead of three: ~70 wave instructions each)
-    const double Ld[3] = {L00, L11, L22};
-    double g = 0.0;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      g = (lane == q) ? gdp[q] * ma.wt : g;
-      g = (lane == 3 + q) ? (gdr[q] * ma.wt - fast_rcp(Ld[q])) * 2.0 * xv[3 + q] : g;
-      g = (lane == 6 + q) ? gdc[q] * ma.wt : g;
-    }
-    st.g = g;
-    finish = __builtin_amdgcn_readfirstlane(st.update(la.p, lane, cost));
-    if (finish != 0x7fffffff) break;
-  }
-  if (lane < 9) la.x[(int64_t)lane * ld + b] = st.x;
-  if (lane == 0) {
-    la.is[(int64_t)IS_DONE * ld + b] = finish != 0x7fffffff;
-    la.is[(int64_t)IS_RET * ld + b] = finish;
-    la.is[(int64_t)IS_K * ld + b] = st.k;
-    la.is[(int64_t)IS_EVALS * ld + b] = st.evals;
-    la.ds[(int64_t)DS_FX * ld + b] = st.fx;
   }
 }
 

@@ -1,4 +1,5 @@
-// Wave-wide reductions of gfx950 on the DPP path (shared by the L-BFGS kernels and the interior-point QP).
+// Wave-wide reductions of gfx950 on the DPP path (shared by the L-BFGS kernels, the one-launch MINCO evaluation
+// and the interior-point QP).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -61,6 +62,46 @@ __device__ __forceinline__ double wave_min_f64(double v) {
   v = fmin(v, dpp_keep_f64<0x142, 0xa>(v));
   v = fmin(v, dpp_keep_f64<0x143, 0xc>(v));
   return last_lane<63>(v);
+}
+
+// a value every lane holds identically (loaded from a wave-uniform address) -> SGPR pair
+__device__ __forceinline__ double uniform_f64(double v) {
+  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)),
+                          __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+// Two problems per wave (32 lanes each): the same scans, chained over the two rows of a half only; each half then
+// reads its total from its own last lane.  Needs the lanes of a HALF to be active together, not the whole wave.
+__device__ __forceinline__ double half_pick(double v) {
+  const double lo = last_lane<31>(v), hi = last_lane<63>(v);
+  return (threadIdx.x & 32) ? hi : lo;
+}
+__device__ __forceinline__ double half_sum(double v) {
+  v += dpp_f64<0x111>(v);
+  v += dpp_f64<0x112>(v);
+  v += dpp_f64<0x114>(v);
+  v += dpp_f64<0x118>(v);
+  v += dpp_f64<0x142, 0xa>(v);
+  return half_pick(v);
+}
+__device__ __forceinline__ double half_max_nonneg(double v) {
+  v = fmax(v, dpp_f64<0x111>(v));
+  v = fmax(v, dpp_f64<0x112>(v));
+  v = fmax(v, dpp_f64<0x114>(v));
+  v = fmax(v, dpp_f64<0x118>(v));
+  v = fmax(v, dpp_f64<0x142, 0xa>(v));
+  return half_pick(v);
+}
+
+template <int CTRL>
+__device__ __forceinline__ double dpp_add(double v) { return v + dpp_f64<CTRL>(v); }
+// sum over the G adjacent lanes of a group (G = 4, 8, 16; every lane of the group ends with the total)
+template <int G>
+__device__ __forceinline__ double group_sum(double v) {
+  v = dpp_add<0xB1>(v);                          // quad_perm [1,0,3,2]
+  v = dpp_add<0x4E>(v);                          // quad_perm [2,3,0,1]
+  if constexpr (G >= 8) v = dpp_add<0x141>(v);   // row_half_mirror
+  if constexpr (G >= 16) v = dpp_add<0x140>(v);  // row_mirror
+  return v;
 }
 
 }  // namespace anet

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-phase cycle counts of the one-launch MINCO L-BFGS kernel (lbfgs_minco_persistent.h), problem 0 of a batch.
+"""Per-phase cycle counts of the one-launch MINCO L-BFGS kernel (lbfgs_minco_persistent.h; its optimiser: lbfgs_resident.h), problem 0 of a batch.
 Needs a library built with the counters compiled in:
     ANET_BUILD_FLAGS=-DANET_PERSIST_PROF python -m allocnet_amd.build --force
     gpurun -- 'python tools/persist_prof.py 2> gpurun_out/persist_prof.txt'
