@@ -23,5 +23,9 @@ from . import voxel_map  # noqa: F401
 from .voxel_map import VoxelMap, gather_boxes_dev  # noqa: F401
 from . import path_search  # noqa: F401
 from .path_search import plan_path, plan_paths, PATH_EXACT, PATH_APPROXIMATE, PATH_INVALID_START  # noqa: F401
+from . import flatness  # noqa: F401
+from .flatness import (FlatnessMap, flat_forward, flat_forward_dev, flat_backward, flat_backward_dev,  # noqa: F401
+                       traj_flat_states, traj_flat_extrema, make_flat_params, make_flat_penalty, minco_flat_cost_grad,
+                       minco_flat_cost_grad_dev, minco_flat_partial_grads_dev)
 
 __version__ = "0.1.0"

@@ -146,6 +146,19 @@ PROTOTYPES = {
     "anet_lbfgs_minco_bounded": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p]),
+    "anet_flat_forward_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] * 9),
+    "anet_flat_forward": (c_int, [c_void_p, c_void_p, c_int64] + [c_void_p] * 8),
+    "anet_flat_backward_dev": (c_int, [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] * 17),
+    "anet_flat_backward": (c_int, [c_void_p, c_void_p, c_int64] + [c_void_p] * 16),
+    "anet_traj_flat_states_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int,
+                                          c_void_p, c_void_p, c_void_p]),
+    "anet_traj_flat_states": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p,
+                                      c_void_p]),
+    "anet_traj_flat_extrema_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int,
+                                           c_void_p, c_void_p]),
+    "anet_traj_flat_extrema": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p]),
+    "anet_minco_flat_partial_grads_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p,
+                                                  c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 
@@ -185,6 +198,19 @@ class Penalty(ctypes.Structure):
     _fields_ = [("rho", c_double), ("w_corridor", c_double), ("w_vel", c_double), ("w_acc", c_double),
                 ("smooth_mu", c_double), ("max_vel", c_double), ("max_acc", c_double),
                 ("res", ctypes.c_int32), ("poly_rows", ctypes.c_int32)]
+
+
+class FlatParams(ctypes.Structure):
+    """struct anet_flat_params: the six arguments of flatness::FlatnessMap::reset."""
+    _fields_ = [("mass", c_double), ("grav", c_double), ("horiz_drag", c_double), ("vert_drag", c_double),
+                ("paras_drag", c_double), ("speed_eps", c_double)]
+
+
+class FlatPenalty(ctypes.Structure):
+    """struct anet_flat_penalty (include/allocnet_amd.h)."""
+    _fields_ = [("w_thrust", c_double), ("w_tilt", c_double), ("w_bdr", c_double), ("smooth_mu", c_double),
+                ("min_thrust", c_double), ("max_thrust", c_double), ("max_tilt", c_double), ("max_bdr", c_double),
+                ("res", ctypes.c_int32)]
 
 
 _lib = None

@@ -43,9 +43,11 @@ int do_propagate(anet_ctx *ctx, int s, const anet::PropArgs &a, hipStream_t st) 
   return anet::with_order(s, [&](auto o) { return launch_prop<decltype(o)::value>(ctx, a, st); });
 }
 
+}  // namespace
+
 // The basis table of k_piece_grad for (order, res): built once per context on the stream that first needs it; other streams are
-// ordered behind the build by its event.
-static int basis_table(anet_ctx *ctx, int s, int res, hipStream_t st, const double **out) {
+// ordered behind the build by its event.  (Declared in api_internal.h: k_flat_piece_grad reads the same table.)
+int basis_table(anet_ctx *ctx, int s, int res, hipStream_t st, const double **out) {
   int rc = ANET_OK;
   *out = nullptr;
   if (res > 4096) return fail(ctx, ANET_ERR_UNSUPPORTED, "anet_penalty.res too large for the basis table");
@@ -75,6 +77,8 @@ static int basis_table(anet_ctx *ctx, int s, int res, hipStream_t st, const doub
   }
   return rc;
 }
+
+namespace {
 
 // The large-batch penalty kernel with the basis-table contractions on the FP64 matrix instructions (csrc/piece_grad_mx.h): built for
 // res = 20, orders 3 and 4 (131 072 x 8 snap pieces: 295 us against 344; 65 536 x 16 jerk pieces: 287 against 296 -- six coefficients

@@ -11,6 +11,7 @@
 //                      (FIRI launches the MVIE kernels of mvie_kernels.h, which one unit only may include)
 //   api_qp.hip         QP assembly, settings, solve, time gradient, VJP
 //   api_voxel.hip      voxel map and route search
+//   api_flatness.hip   differential flatness: states, sampled limits, penalty gradients
 //   piece_grad_unit.hip, qp_ipm_fuse_unit.hip: kernels scheduled for ILP, reached through launch functions
 // Only what two or more units use is here.  Nothing here is exported: the library's dynamic symbols stay the anet_* entry
 // points (and the kernels).
@@ -302,5 +303,9 @@ int resume_parked(anet_ctx *ctx, int64_t batch, const ResumeTail &t, hipStream_t
 int cost_grad_dev_impl(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batch, int64_t ld, const double *head, const double *tail,
                        const double *wps, const double *T, const double *hpolys, const anet_penalty *pen, double *work, double *cost,
                        double *gradP, double *gradT, double *coeffs_out, void *stream, const double *tau);
+
+// the basis table of k_piece_grad for (order, res) (api_cost_grad.hip owns and builds it; layout: minco_kernels.h, at k_piece_grad):
+// k_flat_piece_grad reads its derivative rows 1..3.  The caller has made the context's device current.
+int basis_table(anet_ctx *ctx, int s, int res, hipStream_t st, const double **out);
 
 #pragma GCC visibility pop

@@ -99,3 +99,34 @@ def minco_layer(wps, T, head, tail, s, c, N, B, ctx=None):
     """Batch-minor float64 CUDA tensors with a common row stride ld = T.stride(0): wps ((N-1)*3, ld), T (N, ld),
     head / tail (3c, ld).  Returns coeffs (N*3*2s, ld) and energy (ld,); gradients flow to wps and T."""
     return _MincoSolve.apply(wps, T, head, tail, int(s), int(c), int(N), int(B), ctx)
+
+
+class _FlatMap(torch.autograd.Function):
+    """The flatness map as a differentiable function of (vel, acc, jer, psi, dpsi): forward = anet_flat_forward_dev, backward =
+    anet_flat_backward_dev on the saved inputs (the kernel recomputes the forward intermediates)."""
+
+    @staticmethod
+    def forward(fctx, vel, acc, jer, psi, dpsi, params, n, anet_ctx):
+        from .flatness import flat_forward_dev
+        ins = tuple(t.detach().contiguous() for t in (vel, acc, jer, psi, dpsi))
+        thr, quat, omg = flat_forward_dev(params, *ins, n=n, ctx=anet_ctx)
+        fctx.save_for_backward(*ins)
+        fctx.meta = (params, n, anet_ctx)
+        return thr, quat, omg
+
+    @staticmethod
+    def backward(fctx, g_thr, g_quat, g_omg):
+        from .flatness import flat_backward_dev
+        vel, acc, jer, psi, dpsi = fctx.saved_tensors
+        params, n, anet_ctx = fctx.meta
+        _, vt, at, jt, pst, dpt = flat_backward_dev(params, vel, acc, jer, psi, dpsi, None, None, g_thr.contiguous(),
+                                                    g_quat.contiguous(), g_omg.contiguous(), n=n, ctx=anet_ctx)
+        return vt, at, jt, pst, dpt, None, None, None
+
+
+def flat_layer(vel, acc, jer, psi, dpsi, params, n=None, ctx=None):
+    """Batch-minor float64 CUDA tensors: vel, acc, jer (3, ld), psi, dpsi (ld,); params: anet_flat_params
+    (flatness.make_flat_params) or a FlatnessMap.  Returns thr (ld,), quat (4, ld), omg (3, ld); gradients flow to all five
+    inputs.  Elements [n, ld) are padding: their outputs and gradients are not computed (n defaults to ld)."""
+    from .flatness import _params_of
+    return _FlatMap.apply(vel, acc, jer, psi, dpsi, _params_of(params), n, ctx)

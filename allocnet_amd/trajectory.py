@@ -230,6 +230,32 @@ class Trajectory:
     def checkMaxAccRate(self, maxAccRate):
         return self.getMaxAccRate() < maxAccRate
 
+    # --- the vehicle's own terms: thrust, attitude, body rate through the flatness map (flatness.py) ---------------
+    def getFlatState(self, t, flatmap):
+        """What the reference's process() computes at time t (learning_planning.cpp:236-251): getVel/getAcc/getJer pushed
+        through flatmap.forward with psi = dpsi = 0.  Returns a dict: thr, quat (4,), omg (3,), speed, tilt, bdr; arrays over
+        the queries when t is a sequence."""
+        from .flatness import traj_flat_states
+        co, T = self._arrays()
+        tq = np.atleast_1d(np.asarray(t, dtype=np.float64))
+        o = traj_flat_states(flatmap, co, T, tq[None], ctx=self._ctx)[0]
+        if np.ndim(t) == 0:
+            o = o[0]
+        return {"thr": o[..., 0], "quat": o[..., 1:5], "omg": o[..., 5:8], "speed": o[..., 8], "tilt": o[..., 9],
+                "bdr": o[..., 10]}
+
+    def getFlatExtrema(self, flatmap, res=20):
+        """(min thrust, max thrust, max tilt, max body-rate magnitude) over res + 1 samples of every piece: a sampled check."""
+        from .flatness import traj_flat_extrema
+        co, T = self._arrays()
+        return tuple(float(x) for x in traj_flat_extrema(flatmap, co, T, res, ctx=self._ctx)[0])
+
+    def checkFlatLimits(self, flatmap, min_thrust, max_thrust, max_tilt, max_bdr, res=20):
+        """True when the sampled thrust stays inside (min_thrust, max_thrust) and the sampled tilt and body rate below their limits
+        (strict, like checkMaxVelRate)."""
+        lo, hi, tilt, bdr = self.getFlatExtrema(flatmap, res)
+        return lo > min_thrust and hi < max_thrust and tilt < max_tilt and bdr < max_bdr
+
     # --- junctions (trajectory.hpp:540-574): direct coefficient reads except at the very end
     def getPositions(self):
         N = self.getPieceNum()

@@ -63,6 +63,16 @@ def main():
     T = traj.getTotalDuration()
     print(f"trajectory: {T:.2f} s, start {traj.getPos(0.0)}, end {traj.getPos(T)}, max |v| {traj.getMaxVelRate():.2f}, "
           f"max |a| {traj.getMaxAccRate():.2f}")
+    # what process() publishes at 1 kHz (learning_planning.cpp:236-251): speed, thrust, tilt angle and body-rate magnitude
+    fm = aa.FlatnessMap()
+    fm.reset(1.0, 9.8, 0.7, 0.8, 0.01, 1e-4)                                        # the launch file's vehicle
+    ts = np.linspace(0.0, T, 9)
+    st = traj.getFlatState(ts, fm)
+    for k, t in enumerate(ts):
+        print(f"  t {t:5.2f} s: speed {st['speed'][k]:.3f} m/s, thrust {st['thr'][k]:.3f} N, tilt {st['tilt'][k]:.4f} rad, "
+              f"body rate {st['bdr'][k]:.4f} rad/s")
+    lo_thr, hi_thr, tilt, bdr = traj.getFlatExtrema(fm, res=20)
+    print(f"sampled limits: thrust in [{lo_thr:.3f}, {hi_thr:.3f}] N, tilt <= {tilt:.4f} rad, body rate <= {bdr:.4f} rad/s")
     return 0
 
 

@@ -281,6 +281,80 @@ int anet_minco_cost_grad(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batc
                          double *gradT,  /* [batch][N]      */
                          double *coeffs_out /* [batch][N][3][2s] or NULL */);
 
+/* ---- differential flatness: states, limits, penalty gradients ------------------------------ */
+/* Replaces flatness::FlatnessMap (gcopter/flatness.hpp:37-260): reset's six parameters, forward (:54-134) from velocity,
+ * acceleration, jerk, yaw and yaw rate to thrust, attitude quaternion (w, x, y, z) and body rate, and backward (:136-260), the
+ * adjoint of that map.  With w = (1 + cp sqrt(|v|^2 + eps)) v,  zu = a + (dh/m) w + g e3,  z = zu / |zu|:
+ *   thr = z . (m a + dv w + m g e3),  quat = tilt(z) * yaw(psi),  omg = body rate of (z, dz/dt, psi, dpsi).
+ * The adjoint is derived from this forward and pinned by automatic differentiation and finite differences.
+ * Singular only at z = -e3 (inverted thrust direction), as the reference.                                                   */
+typedef struct anet_flat_params {
+  double mass;       /* vehicle mass, > 0                       (reset: vehicle_mass)               */
+  double grav;       /* gravitational acceleration              (gravitational_acceleration)        */
+  double horiz_drag; /* dh                                      (horitonral_drag_coeff)             */
+  double vert_drag;  /* dv                                      (vertical_drag_coeff)               */
+  double paras_drag; /* cp                                      (parasitic_drag_coeff)              */
+  double speed_eps;  /* eps under the square root of the speed, > 0 (speed_smooth_factor)           */
+} anet_flat_params;
+
+/* Pointwise, one element per lane.  vel, acc, jer: [3][ld]; psi, dpsi: [ld] or NULL (NULL = 0; both NULL: no trigonometry, the
+ * call process() makes, learning_planning.cpp:243).  thr [ld], quat [4][ld] (w, x, y, z), omg [3][ld].                      */
+int anet_flat_forward_dev(anet_ctx *ctx, const anet_flat_params *params, int64_t batch, int64_t ld, const double *vel,
+                          const double *acc, const double *jer, const double *psi, const double *dpsi, double *thr, double *quat,
+                          double *omg, void *stream);
+/* Host variant: vel, acc, jer [batch][3]; psi, dpsi [batch] or NULL; thr [batch], quat [batch][4], omg [batch][3]. */
+int anet_flat_forward(anet_ctx *ctx, const anet_flat_params *params, int64_t batch, const double *vel, const double *acc,
+                      const double *jer, const double *psi, const double *dpsi, double *thr, double *quat, double *omg);
+/* FlatnessMap::backward at the given inputs (stateless: the forward intermediates are recomputed).  Upstream gradients
+ * thr_grad [ld], quat_grad [4][ld], omg_grad [3][ld]; pos_grad, vel_grad [3][ld] pass through additively (either may be NULL = 0).
+ * Totals: vel_total, acc_total, jer_total [3][ld]; pos_total [3][ld], psi_total, dpsi_total [ld] may be NULL (not written).  */
+int anet_flat_backward_dev(anet_ctx *ctx, const anet_flat_params *params, int64_t batch, int64_t ld, const double *vel,
+                           const double *acc, const double *jer, const double *psi, const double *dpsi, const double *pos_grad,
+                           const double *vel_grad, const double *thr_grad, const double *quat_grad, const double *omg_grad,
+                           double *pos_total, double *vel_total, double *acc_total, double *jer_total, double *psi_total,
+                           double *dpsi_total, void *stream);
+/* Host variant, element-major as anet_flat_forward. */
+int anet_flat_backward(anet_ctx *ctx, const anet_flat_params *params, int64_t batch, const double *vel, const double *acc,
+                       const double *jer, const double *psi, const double *dpsi, const double *pos_grad, const double *vel_grad,
+                       const double *thr_grad, const double *quat_grad, const double *omg_grad, double *pos_total,
+                       double *vel_total, double *acc_total, double *jer_total, double *psi_total, double *dpsi_total);
+
+/* Along trajectories (psi = dpsi = 0, as in the reference): the piece location of anet_traj_eval, then velocity, acceleration and
+ * jerk at each query and the forward map.  Per query 11 fields: thr, q0..q3, omg0..2, speed = |v|, tilt = acos(1 - 2 (q1^2 + q2^2)),
+ * bdr = |omg| -- the last three and thr are what process() publishes (learning_planning.cpp:249-251).
+ * out: [nq*11][ld] (dev, query-major then field) / [batch][nq][11] (host).                                                    */
+#define ANET_FLAT_STATE_FIELDS 11
+int anet_traj_flat_states_dev(anet_ctx *ctx, const anet_flat_params *params, int s, int n_pieces, int64_t batch, int64_t ld,
+                              const double *coeffs, const double *T, int nq, const double *tq, double *out, void *stream);
+int anet_traj_flat_states(anet_ctx *ctx, const anet_flat_params *params, int s, int n_pieces, int64_t batch, const double *coeffs,
+                          const double *T, int nq, const double *tq, double *out);
+/* Minimum thrust, maximum thrust, maximum tilt and maximum body-rate magnitude of each trajectory over the samples
+ * t = j T_i / res, j = 0..res, of every piece (both ends included).  A SAMPLED check: the flat outputs are not polynomials in t, so
+ * unlike anet_traj_max_rate nothing bounds them between the samples.  out: [4][ld] (dev) / [batch][4] (host).               */
+int anet_traj_flat_extrema_dev(anet_ctx *ctx, const anet_flat_params *params, int s, int n_pieces, int64_t batch, int64_t ld,
+                               const double *coeffs, const double *T, int res, double *out, void *stream);
+int anet_traj_flat_extrema(anet_ctx *ctx, const anet_flat_params *params, int s, int n_pieces, int64_t batch, const double *coeffs,
+                           const double *T, int res, double *out);
+
+/* Thrust, tilt and body-rate limits as a penalty of the MINCO objective, with the quadrature and the smoothedL1 of J_pen:
+ *   J_flat = sum_i (T_i/res) sum_{j<res} [ w_thrust (phi(thr - max_thrust) + phi(min_thrust - thr))
+ *                                        + w_tilt phi(cos(max_tilt) - cos(tilt)) + w_bdr phi(|omg|^2 - max_bdr^2) ]
+ * at t = j T_i / res with psi = dpsi = 0;  cos(tilt) = 1 - 2 (q1^2 + q2^2).                                                  */
+typedef struct anet_flat_penalty {
+  double w_thrust, w_tilt, w_bdr;
+  double smooth_mu;  /* smoothedL1 mu, > 0 (in the units of each row: thrust, cosine, squared rate) */
+  double min_thrust, max_thrust; /* min_thrust < max_thrust                                        */
+  double max_tilt;   /* radians, in (0, pi)                                                        */
+  double max_bdr;    /* body-rate magnitude                                                        */
+  int32_t res;       /* samples per piece, >= 1                                                    */
+} anet_flat_penalty;
+/* Partial gradients of J_flat w.r.t. the coefficients and durations, in the layout of anet_minco_partial_grads_dev; orders 3 and
+ * 4 (ANET_ERR_UNSUPPORTED otherwise).  accumulate = 0: gdC, gdT, piece_cost are written; != 0: J_flat's share is ADDED to them, so
+ * that energy, corridor, box and flatness terms go through one anet_minco_propagate_grad_dev.  piece_cost may be NULL.       */
+int anet_minco_flat_partial_grads_dev(anet_ctx *ctx, const anet_flat_params *params, const anet_flat_penalty *pen, int s,
+                                      int n_pieces, int64_t batch, int64_t ld, const double *coeffs, const double *T,
+                                      int accumulate, double *gdC, double *gdT, double *piece_cost, void *stream);
+
 /* ---- QP assembly (the reference's own formulation) ----------------------------------------- */
 /* Replaces the assembly part of QPSolver::solve (planner/qp_solver.hpp:61-296: setOrder/zero_A_,
  * get_t_state, equality rows :139-177, objective :180-242, inequality rows :244-296) and its Python
