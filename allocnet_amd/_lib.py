@@ -159,6 +159,11 @@ PROTOTYPES = {
     "anet_traj_flat_extrema": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p]),
     "anet_minco_flat_partial_grads_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p,
                                                   c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "anet_timenet_create": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "anet_timenet_destroy": (None, [c_void_p]),
+    "anet_timenet_device_bytes": (c_int64, [c_void_p]),
+    "anet_timenet_forward_dev": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_double, c_int] + [c_void_p] * 5),
+    "anet_timenet_forward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_double, c_int] + [c_void_p] * 4),
 }
 
 

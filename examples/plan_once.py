@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """One pass of the reference's online flow (LearningPlanner::plan + callModel, learning_planner.hpp:240-300, 140-236) on the
-MI355X path, with a constant-speed time allocation standing in for the network:
+MI355X path.  Without --weights a constant-speed time allocation stands in for the network; with it the segment times come
+from the time-allocation network on the device (allocnet_amd.TimeAllocNet):
 
     route -> convexCover -> shortCut -> planner form -> [network: segment times] -> QPSolver::solve -> Trajectory
 
-    python examples/plan_once.py          # needs a GPU; prints the stages and their wall times
+    python examples/plan_once.py                    # needs a GPU; prints the stages and their wall times
+    python examples/plan_once.py --weights FILE     # FILE: a weights file of TimeAllocNet.save, or an exported TorchScript model
 """
+import argparse
 import os
 import sys
 import time
@@ -17,6 +20,9 @@ import allocnet_amd as aa  # noqa: E402
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--weights", default=None, help="weights of the time-allocation network (default: constant-speed times)")
+    args = ap.parse_args()
     rng = np.random.default_rng(17)
     route = [np.array(p, dtype=float) for p in ([0, 0, 1], [3.5, 1, 1.5], [6, 4, 1], [9, 4.5, 2])]
     lo, hi = [-3, -3, 0], [12, 8, 4]
@@ -47,6 +53,17 @@ def main():
     state, corridor = aa.pack_model_inputs(ini, fin, [hp[i, :rows[i]] for i in range(seg)])   # what callModel feeds the network
     length = np.linalg.norm(np.diff(np.array(route), axis=0), axis=1).sum()
     times = np.full(seg, length / seg / 1.0, dtype=np.float32)                      # <- minsnap_conv_lstm_network.forward(inputs)
+    if args.weights:
+        with open(args.weights, "rb") as f:
+            own = f.read(8) == aa.time_net.MAGIC
+        net = aa.TimeAllocNet.load(args.weights) if own else aa.TimeAllocNet.from_torchscript(args.weights)
+        net.forward(state, corridor)                                                # warm-up (upload, module load)
+        tn = time.perf_counter()
+        times, count = net.forward(state, corridor)                                 # :174
+        print(f"network {1e3 * (time.perf_counter() - tn):.2f} ms: count {int(count)}, times {times}")
+        if (times[:seg] < 1e-10).any():
+            print(f"time and seg does not fit, the segment is {seg}")              # :181-189
+            return 1
     t3 = time.perf_counter()
     solver = aa.QPSolver(aa.QPConfig(MaxVelBox=4.0, MaxAccBox=6.0, ConstRes=20))
     solver.setOrder(4)

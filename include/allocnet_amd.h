@@ -816,6 +816,42 @@ int anet_voxel_path_extract_dev(anet_ctx *ctx, const anet_voxel_grid *grid, cons
                                 const double *starts, const double *goals, int64_t n_problems, void *work, int64_t max_points,
                                 double *paths, int32_t *n_points, double *cost, int32_t *status, void *stream);
 
+/* ---- the time-allocation network (network/utils/learning/minsnap_network_conv_lstm.py:37-88, 114-187) ---- */
+/* Inference of the exported model the planner loads (LearningPlanner::loadModel / callModel), batched, all arithmetic in float32:
+ *   state  (9, 2)     -> Conv1d(9->8, k 3, pad 1) -> ReLU -> MaxPool1d(2) -> Linear(8->6)
+ *   hpolys (50, 4, L) -> Conv2d(50->16, 3x3, pad 1) -> ReLU -> MaxPool2d(2) -> MaxPool2d(2) -> Flatten -> Linear(->32)
+ *   x = [6 | 32], the same at every step; h = c = 0; L steps of an LSTM cell (hidden 256, gates i, f, g, o);
+ *   tf_k = w_t . h + b_t, stop_k = sigmoid(w_s . h + b_s); count = 1 + first k with stop_k > threshold (L if none);
+ *   times = tf[:count], zero after.  The export stops at threshold 0.5, forward_batch at 0.42.
+ * The handle owns the device copy of the weights (the recurrent matrices repacked into the order the kernels read) and a grow-only
+ * workspace; it belongs to the context it was created on and is destroyed by its owner (before or after the context).
+ * weights: ANET_TIMENET_TENSORS host pointers, float32, natural (state-dict) shapes, in this order:
+ *   state_input_module.0.weight (8,9,3), .0.bias (8), .4.weight (6,8), .4.bias (6),
+ *   hpoly_input_module.0.weight (16,50,3,3), .0.bias (16), .5.weight (32, 16 (L/4)), .5.bias (32),
+ *   output_module.weight_ih_l0 (1024,38), weight_hh_l0 (1024,256), bias_ih_l0 (1024), bias_hh_l0 (1024),
+ *   tfs_output_layer.weight (1,256), .bias (1), stop_token_output_layer.0.weight (1,256), .0.bias (1).
+ * seq_len must be 5 or 10 and hidden 256 (ANET_ERR_UNSUPPORTED otherwise).                                                       */
+#define ANET_TIMENET_TENSORS 16
+typedef struct anet_timenet anet_timenet;
+int anet_timenet_create(anet_ctx *ctx, int seq_len, int hidden, const float *const *weights, anet_timenet **out);
+void anet_timenet_destroy(anet_timenet *net);
+/* bytes of device memory the handle holds (weights, workspace, staging of the host entry point) */
+int64_t anet_timenet_device_bytes(const anet_timenet *net);
+/* flags of the forward calls */
+#define ANET_TIMENET_KEEP_PADDING 1 /* do not skip zero rows / zero polytopes (the results are the same bits; kept for the test) */
+#define ANET_TIMENET_FORM_SINGLE 2  /* one workgroup per problem, a thread per hidden unit, whatever the batch                   */
+#define ANET_TIMENET_FORM_TILE 4    /* one workgroup per 32 problems on the f32 matrix instruction, whatever the batch           */
+/* without a FORM flag: batches up to this take the single form, larger ones the tile form */
+#define ANET_TIMENET_SINGLE_MAX 1024
+/* state [batch][9][2], hpolys [batch][50][4][seq_len] float32 in the reference's layout (the tensors of callModel, stacked);
+ * times [batch][seq_len], count [batch]; tf, stop [batch][seq_len] (all steps, whatever the count) or NULL.
+ * _dev: device pointers, asynchronous on `stream`, no synchronisation, and no allocation after the first call at a batch size.
+ * The two forms agree in count and within the tolerance of DESIGN.md 8g, not bit for bit.                                        */
+int anet_timenet_forward_dev(anet_ctx *ctx, anet_timenet *net, int seq_len, int64_t batch, const float *state, const float *hpolys,
+                             double threshold, int flags, float *times, float *tf, float *stop, int32_t *count, void *stream);
+int anet_timenet_forward(anet_ctx *ctx, anet_timenet *net, int seq_len, int64_t batch, const float *state, const float *hpolys,
+                         double threshold, int flags, float *times, float *tf, float *stop, int32_t *count);
+
 /* ---- multi-GPU: all-gather of the per-trajectory costs over RCCL / xGMI --------------------------- */
 /* Trajectories are independent, so a batch shards contiguously across GPUs (one process and one
  * context per GPU) with no collective inside a solve; the only exchange the path has is this
