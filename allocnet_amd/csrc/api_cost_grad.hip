@@ -131,8 +131,7 @@ int cost_grad_dev_impl(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batch,
     const double *tab = nullptr;
     if ((rc = basis_table(ctx, s, pen->res, (hipStream_t)stream, &tab))) return rc;
     anet::FusedArgs fa{head, tail, wps, T, pen->poly_rows > 0 ? hpolys : nullptr, cost, gradP, gradT, coeffs_out, tau, batch, ld,
-                       n_pieces, c, anet::Penalty{pen->rho, pen->w_corridor, pen->w_vel, pen->w_acc, pen->smooth_mu, pen->max_vel,
-                                                  pen->max_acc, pen->res, pen->poly_rows}, 0};
+                       n_pieces, c, anet::to_kernel_penalty(*pen, pen->poly_rows), 0};
 #ifdef ANET_FUSED_PROF
     static long long *d_fprof = nullptr;
     if (!d_fprof) ANET_HIP(ctx, hipMalloc((void **)&d_fprof, 16 * sizeof(long long)));
@@ -195,8 +194,7 @@ int anet_minco_partial_grads_dev(anet_ctx *ctx, int s, int n_pieces, int64_t bat
   a.coeffs = coeffs; a.T = T; a.hpolys = (pen && pen->poly_rows > 0) ? hpolys : nullptr;
   a.gdC = gdC; a.gdT = gdT; a.pcost = piece_cost;
   a.B = batch; a.ld = ld; a.N = n_pieces; a.with_energy = with_energy ? 1 : 0; a.with_penalty = pen ? 1 : 0;
-  if (pen) a.pp = anet::Penalty{pen->rho, pen->w_corridor, pen->w_vel, pen->w_acc, pen->smooth_mu,
-                               pen->max_vel, pen->max_acc, pen->res, pen->poly_rows};
+  if (pen) a.pp = anet::to_kernel_penalty(*pen, pen->poly_rows);
   const dim3 grid((unsigned)((batch + 255) / 256), (unsigned)n_pieces), block(256);
   hipStream_t st = (hipStream_t)stream;
   const double *tab = nullptr;

@@ -16,7 +16,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "minco_kernels.h"  // smoothed_l1
+#include "minco_core.h"     // with_order
+#include "penalty_terms.h"  // smoothed_l1, normalised_coeffs
 
 namespace anet {
 
@@ -402,7 +403,7 @@ __device__ __forceinline__ double add_unfused(double old, double v) {
 // One lane per (trajectory, piece), blockIdx.y = piece, as k_piece_grad.
 //   J_flat = sum_i (T_i/res) sum_{j<res} [ w_thr (phi(thr - thr_max) + phi(thr_min - thr)) + w_tilt phi(cos(tilt_max) - cos(tilt))
 //                                        + w_bdr phi(|omg|^2 - bdr_max^2) ]   at t_j = j T_i / res, psi = dpsi = 0,
-// phi = smoothed_l1 (minco_kernels.h), cos(tilt) = 1 - 2 (q1^2 + q2^2).  Writes (accumulate: adds) the partial gradients w.r.t. the
+// phi = smoothed_l1 (penalty_terms.h), cos(tilt) = 1 - 2 (q1^2 + q2^2).  Writes (accumulate: adds) the partial gradients w.r.t. the
 // piece's coefficients and duration, and the piece's share of J_flat.
 // Normalised time as in k_piece_grad: with c~_k = c_k T^k, d^d p / dt^d (t_j) = T^-d sum_col c~[col] tab[j][d][col].  The rows
 // d = 1, 2, 3 are read from k_piece_grad's basis table (wave-uniform index: scalar loads); the snap row d = 4, which only the
@@ -422,13 +423,12 @@ __global__ void __launch_bounds__(256) k_flat_piece_grad(FlatPieceGradArgs a, co
   double ct[3][D];  // c~
   {
     const double *cm = a.coeffs + (int64_t)(i * 3 * D) * ld + b;
-    double tk = 1.0;
+    double c[3][D];
 #pragma unroll
-    for (int col = D - 1; col >= 0; --col) {
+    for (int ax = 0; ax < 3; ++ax)
 #pragma unroll
-      for (int ax = 0; ax < 3; ++ax) ct[ax][col] = cm[(int64_t)(ax * D + col) * ld] * tk;
-      tk *= Ti;
-    }
+      for (int col = 0; col < D; ++col) c[ax][col] = cm[(int64_t)(ax * D + col) * ld];
+    normalised_coeffs<S>(c, Ti, ct);
   }
   double gN[3][D];
 #pragma unroll

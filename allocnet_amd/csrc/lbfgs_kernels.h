@@ -3,7 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "minco_kernels.h"
+#include "minco_core.h"  // forward_T, backward_T
 #include "lbfgs_step.h"
 #include "wave_ops.h"
 

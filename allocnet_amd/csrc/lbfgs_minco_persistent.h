@@ -638,7 +638,8 @@ __device__ __forceinline__ void persist_eval(PersistLds<S, NB> &Lm, const double
   PERSIST_PHASE();
   // ---- E4: penalty functional, lanes = (piece, sample group).  A lane holds NS samples of its piece at a time: their
   //      positions first, then the corridor rows are walked ONCE for all of them (four rows per LDS round trip), then the
-  //      velocity / acceleration limits and the gradient per sample.  Same arithmetic as k_piece_grad (minco_kernels.h):
+  //      velocity / acceleration limits and the gradient per sample.  The arithmetic of k_piece_grad, from the same pieces
+  //      (penalty_terms.h; the corridor rows keep E4's own one-addition form of F, see corridor_row_terms there):
   //      * everything in units of mu: the rows are staged divided by mu, u = a.p - b, the smoothed L1 is mu F(u) with
   //        F(u) = uc^3 (1 - uc/2) + max(u - 1, 0), F' = uc^2 (3 - 2 uc), uc = clamp(u, 0, 1); a limit is
   //        u = |a1| kv - cv straight from the normalised-time sum a1 = sum c~ tb' (kv = 1 / (T mu), cv = vmax / mu);
@@ -661,21 +662,11 @@ __device__ __forceinline__ void persist_eval(PersistLds<S, NB> &Lm, const double
         const Penalty pp = a.pp;
         const double Ti = Lm.T[i];
         const double inv_mu = a.inv_mu, inv_res = a.inv_res;  // (host-side reciprocals: an IEEE division is ~30 wave instructions)
-        const double step = Ti * inv_res;
-        const double rT = Lm.r[i], rT2 = rT * rT;  // (1 / T_i of E1)
-        const double wcm = pp.wc * pp.mu, wvm = pp.wv * pp.mu, wam = pp.wa * pp.mu;
-        const double kv = rT * inv_mu, ka = rT2 * inv_mu, cv = pp.vmax * inv_mu, ca = pp.amax * inv_mu;
-        const double K0 = step * wcm, K1 = step * rT * pp.wv, K2 = step * rT2 * pp.wa;
+        const double rT = Lm.r[i];  // (1 / T_i of E1)
+        const PieceScales k = piece_scales(pp, Ti, rT, inv_mu, inv_res);
+        const double K0 = k.step * k.wcm;  // (the rows are staged divided by mu)
         double ct[3][D];
-        {
-          double tk = 1.0;
-#pragma unroll
-          for (int col = D - 1; col >= 0; --col) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) ct[q][col] = Lm.co[i][q][col] * tk;
-            tk *= Ti;
-          }
-        }
+        normalised_coeffs<S>(Lm.co[i], Ti, ct);
         const int M4 = a.hpolys ? (a.M + 3) & ~3 : 0;  // rows per piece in LDS (divided by mu), zero rows up to a multiple of four
         const double *rp = rows + (size_t)i * (4 * (size_t)M4 + 4);
         const bool all_ok = pp.res % (G * NS) == 0;  // every lane has a full set of samples in every pass
@@ -748,25 +739,18 @@ __device__ __forceinline__ void persist_eval(PersistLds<S, NB> &Lm, const double
               for (int col = 0; col < D - 2; ++col) x2 = __builtin_fma(ct[q][col], tb2[col], x2);
               a1[q] = x1;
               a2[q] = x2;
-              worst = fmax(worst, fmax(__builtin_fma(fabs(x1), kv, -cv), __builtin_fma(fabs(x2), ka, -ca)));
+              worst = fmax(worst, fmax(__builtin_fma(fabs(x1), k.kv, -k.cv), __builtin_fma(fabs(x2), k.ka, -k.ca)));
             }
             if (!all_ok) worst = ok[sI] ? worst : 0.0;
-            double cost = wcm * Fs[sI];
-            if (__any(worst > 0.0)) {  // only one of +v, -v (+a, -a) can be violated: the slope has the sign of a1 (a2)
+            double cost = k.wcm * Fs[sI];
+            if (__any(worst > 0.0)) {
               const double live = (all_ok || ok[sI]) ? 1.0 : 0.0;
 #pragma unroll
               for (int q = 0; q < 3; ++q) {
-                double f, df;
-                smoothed_l1_unit(__builtin_fma(fabs(a1[q]), kv, -cv), f, df);
-                if (!all_ok) { f *= live; df *= live; }
-                cost = __builtin_fma(wvm, f, cost);
-                const double s1 = K1 * copysign(df, a1[q]);
-                Rs1 = __builtin_fma(s1, a1[q], Rs1);
-                smoothed_l1_unit(__builtin_fma(fabs(a2[q]), ka, -ca), f, df);
-                if (!all_ok) { f *= live; df *= live; }
-                cost = __builtin_fma(wam, f, cost);
-                const double s2 = K2 * copysign(df, a2[q]);
-                Rs2 = __builtin_fma(s2, a2[q], Rs2);
+                double s1, s2;
+                limit_terms_masked(k, a1[q], a2[q], cost, Rs1, Rs2, s1, s2, [&](double &f, double &df) {
+                  if (!all_ok) { f *= live; df *= live; }
+                });
 #pragma unroll
                 for (int col = 0; col < D - 1; ++col) gC[q][col] = __builtin_fma(s1, tb1[col], gC[q][col]);
 #pragma unroll
@@ -784,24 +768,10 @@ __device__ __forceinline__ void persist_eval(PersistLds<S, NB> &Lm, const double
             }
           }
         }
-        pc = step * csum;
-        {  // d/dT at fixed c: the quadrature weight T/res and the sample times tau_j T (gC still holds d/dc~)
-          double acc = 0.0;
-#pragma unroll
-          for (int q = 0; q < 3; ++q)
-#pragma unroll
-            for (int col = 0; col < D - 1; ++col) acc = __builtin_fma(ct[q][col] * (double)(D - 1 - col), gC[q][col], acc);
-          gT = csum * inv_res + rT * (acc - __builtin_fma(2.0, Rs2, Rs1));
-        }
-        {  // d/dc = T^k d/dc~
-          double tk = 1.0;
-#pragma unroll
-          for (int col = D - 1; col >= 0; --col) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) gC[q][col] *= tk;
-            tk *= Ti;
-          }
-        }
+        pc = k.step * csum;
+        // (gC still holds d/dc~ here; then d/dc = T^k d/dc~)
+        gT = duration_grad(csum, inv_res, rT, sample_time_moment<S, D - 1>(ct, gC), Rs1, Rs2);
+        scale_coeff_grad<S>(gC, Ti);
       }
       // sum over the sample groups of the piece (all lanes take part)
 #pragma unroll

@@ -10,9 +10,12 @@
 // pivoting needed, no square roots) and each axis is a forward/backward sweep.  This is ~4x
 // fewer FP64 operations than the 2sN x 2sN banded collocation LU and needs no pivoting, which
 // is what lets one lane own one trajectory with the factor resident in registers.
+// Also here, at the end, because every unit that launches an order-templated kernel includes this header and not all of them
+// include minco_kernels.h: with_order, the HOST ladder from a run-time order to its template argument.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "minco_tables.h"
 
 namespace anet {
@@ -446,6 +449,15 @@ __device__ __forceinline__ double dforward_T(double tau) {
 }
 __device__ __forceinline__ double backward_T(double T) {
   return T > 1.0 ? sqrt(2.0 * T - 1.0) - 1.0 : 1.0 - sqrt(2.0 / T - 1.0);
+}
+
+// The order ladder of the host launches: f(std::integral_constant<int, S>{}) with S = s for s = 2, 3 and S = 4 otherwise (the
+// callers have checked s)
+template <class F>
+decltype(auto) with_order(int s, F &&f) {
+  if (s == 2) return f(std::integral_constant<int, 2>{});
+  if (s == 3) return f(std::integral_constant<int, 3>{});
+  return f(std::integral_constant<int, 4>{});
 }
 
 }  // namespace anet

@@ -482,16 +482,7 @@ __global__ void __launch_bounds__(MX ? 512 : 256, 1) k_minco_cost_grad_fused(Fus
     const int M = mx_M, nrb = mx_nrb;
     double *const lr = mx_row + wave * 16 * MXTST;
     double AE, AP;  // energy part: the A operands of k_piece_grad_mx (a row of the energy Hessian's integers, the derivative factors)
-    {
-      const int ie = lane & 3, ke = lane >> 4;
-      double fi = 1.0, fk = 1.0;
-      for (int e = 0; e < S; ++e) {
-        fi *= (double)(D - 1 - ie - e);
-        fk *= (double)(D - 1 - ke - e);
-      }
-      AE = (ie < S && ke < S) ? 2.0 * fi * fk / (double)(2 * S - 1 - ie - ke) : 0.0;
-      AP = ke < S ? fk : 0.0;
-    }
+    mx_energy_operands<S>(lane, AE, AP);
     const bool has1 = 4 + r < D;
     auto park_rows = [&]() {
 #pragma unroll
@@ -580,28 +571,15 @@ __global__ void __launch_bounds__(MX ? 512 : 256, 1) k_minco_cost_grad_fused(Fus
                              },
                              gN, csum, Rs1, Rs2, rT, step);
       ANET_FP(6);
-      double acc = 0.0;
-#pragma unroll
-      for (int ax = 0; ax < 3; ++ax) {
-        acc = __builtin_fma(cb[ax][0] * (double)(D - 1 - r), gN[ax][0], acc);
-        acc = __builtin_fma(cb[ax][1] * (double)(D - 5 - r), gN[ax][1], acc);
-      }
-      double gT = __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, csum * inv_res + rT * (acc - __builtin_fma(2.0, Rs2, Rs1)), 0.0, 0, 0, 0);
-      const double pc = __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, step * csum, 0.0, 0, 0, 0);
-      const double tsel0 = mx_sel4(r, tp[D - 1], tp[D - 2], tp[D - 3], tp[D - 4]);
-      const double tsel1 = D == 8 ? mx_sel4(r, tp[3], tp[2], tp[1], tp[0]) : mx_sel4(r, tp[1], tp[0], 0.0, 0.0);
       // (cb already carries the powers: the columns' d/dc = T^k d/dc~ need them once more)
-      const double rTS = S == 4 ? (rT * rT) * (rT * rT) : rT * (rT * rT);
-      const double TA = tsel0 * (S == 4 ? rT * (rT * rT) : rT * rT);
+      double tsel0, tsel1, g0[3], g1[3], gT, pc;
+      mx_column_powers<D>(r, tp, tsel0, tsel1);
+      mx_pair_epilogue<S>(r, cb, gN, csum, Rs1, Rs2, rT, step, inv_res, tsel0, tsel1, true, AE, AP, g0, g1, gT, pc);
       wave_sync();  // (every lane of the pair has read c~ from the hand-over rows: they take d/dc now)
 #pragma unroll
       for (int ax = 0; ax < 3; ++ax) {
-        const double ye = cb[ax][0] * rTS;
-        const double e = __builtin_amdgcn_mfma_f64_4x4x4f64(AE, ye, 0.0, 0, 0, 0);
-        const double ps = __builtin_amdgcn_mfma_f64_4x4x4f64(AP, ye, 0.0, 0, 0, 0);
-        gT = __builtin_fma(ps, ps, gT);
-        lds[(ROW_GX + ax * D + r) * PST + pair] = __builtin_fma(e, TA, gN[ax][0] * tsel0);
-        if (has1) lds[(ROW_GX + ax * D + 4 + r) * PST + pair] = gN[ax][1] * tsel1;
+        lds[(ROW_GX + ax * D + r) * PST + pair] = g0[ax];
+        if (has1) lds[(ROW_GX + ax * D + 4 + r) * PST + pair] = g1[ax];
       }
       wave_sync();
       ANET_FP(7);

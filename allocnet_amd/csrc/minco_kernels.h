@@ -6,6 +6,8 @@
 #include <stdint.h>
 #include <type_traits>
 #include "minco_core.h"
+#include "penalty_terms.h"
+#include "wave_ops.h"  // lane_pair_swap, pair_sum
 
 namespace anet {
 
@@ -159,12 +161,6 @@ __global__ void __launch_bounds__(kSolveBlock) k_minco_solve_axis(SolveArgs a) {
 // block and right-hand side (a DPP swap of adjacent lanes, the partner's values with the signs of the reversal) and both finish
 // the middle node for themselves.  Half the sequential depth, twice the waves: the shape of batches that leave most SIMDs empty
 // (1024 trajectories: 9.4 -> see DESIGN 4.1).  Lane order: 6 lanes per trajectory (axis, role), ten trajectories per wave.
-__device__ __forceinline__ double lane_pair_swap(double v) {  // the value of the other lane of the pair (lanes 2k, 2k+1)
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(0, lo, 0xB1, 0xf, 0xf, true);  // quad_perm [1,0,3,2]
-  hi = __builtin_amdgcn_update_dpp(0, hi, 0xB1, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
 template <int S, int NB, int NPC>
 __global__ void __launch_bounds__(kSolveBlock) k_minco_solve_axis_two(SolveArgs a) {
   static_assert(NB % 2 == 0 && NB >= 2, "an even number of pieces");
@@ -244,37 +240,7 @@ __global__ void __launch_bounds__(kSolveBlock) k_minco_solve_axis_two(SolveArgs 
 // ------------------------------------------------------------------------------------------
 // cost / gradient path: partial gradients per piece, then adjoint propagation per trajectory
 // ------------------------------------------------------------------------------------------
-struct Penalty {
-  double rho, wc, wv, wa, mu, vmax, amax;
-  int res, M;
-};
-
-// firi::smoothedL1 (gcopter/firi.hpp:60-84), 0 below 0.
-__device__ __forceinline__ void smoothed_l1(double mu, double inv_mu, double x, double &f, double &df) {
-  const double xd = x * inv_mu, sq = xd * xd, mm = __builtin_fma(-0.5, x, mu);
-  double fm = mm * sq * xd, dm = sq * __builtin_fma(-0.5, xd, 3.0 * mm * inv_mu);
-  const bool hi = x > mu, neg = x < 0.0;
-  f = neg ? 0.0 : (hi ? x - 0.5 * mu : fm);
-  df = neg ? 0.0 : (hi ? 1.0 : dm);
-}
-
-// The same function without selects (the penalty kernel evaluates this for every row x sample):
-// with xc = clamp(x, 0, mu) the cubic piece gives 0 below 0 and mu/2, slope 1 at mu, so
-//   f = cubic(xc) + max(x - mu, 0),  df = cubic'(xc).
-__device__ __forceinline__ void smoothed_l1_clamped(double mu, double inv_mu, double x, double &f, double &df) {
-  const double xc = fmin(fmax(x, 0.0), mu);
-  const double xd = xc * inv_mu, sq = xd * xd, mm = __builtin_fma(-0.5, xc, mu);
-  f = __builtin_fma(mm * sq, xd, fmax(x - mu, 0.0));
-  df = sq * __builtin_fma(-0.5, xd, (3.0 * inv_mu) * mm);
-}
-
-// F and F' of the note in k_piece_grad: smoothed L1 of x = mu u is mu F(u), its slope F'(u)
-__device__ __forceinline__ void smoothed_l1_unit(double u, double &F, double &dF) {
-  const double w = fmax(u, 0.0), uc = fmin(w, 1.0), sq = uc * uc;
-  F = __builtin_fma(sq * uc, __builtin_fma(-0.5, uc, 1.0), w - uc);
-  dF = sq * __builtin_fma(-2.0, uc, 3.0);
-}
-
+// (struct Penalty, the smoothed L1 and the terms of J_pen: penalty_terms.h)
 struct PieceGradArgs {
   const double *coeffs, *T, *hpolys;
   double *gdC, *gdT, *pcost;
@@ -297,12 +263,7 @@ struct PieceGradArgs {
 // the even row chunks, lane 1 the box rows and the odd chunks; the partial gradients are summed across the pair
 // with a DPP swap.  Same work, half the dependent chain per lane and twice the waves -- what counts when the
 // batch leaves one wave per SIMD.
-__device__ __forceinline__ double pair_sum(double v) {  // v + the value of the other lane of the pair (lanes 2k, 2k+1)
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(0, lo, 0xB1, 0xf, 0xf, true);  // quad_perm [1,0,3,2]
-  hi = __builtin_amdgcn_update_dpp(0, hi, 0xB1, 0xf, 0xf, true);
-  return v + __hiloint2double(hi, lo);
-}
+// (pair_sum: wave_ops.h)
 
 // A row of the basis table (D <= 8 doubles, wave-uniform address) through a scalar load the COMPILER does not track: request()
 // issues it, await() is the s_waitcnt the values may be read behind.  (Six-column rows load eight: the table's rows are 4 D apart.)
@@ -353,27 +314,17 @@ __device__ __forceinline__ void piece_penalty_part(const Penalty &pp_in, const d
   //    with v = a1 / T, a = a2 / T^2 that is (1/T) (sum s1 a1 + 2 sum s2 a2): two accumulators, scaled once.
   const Penalty pp = pp_in;
   const double inv_mu = 1.0 / pp.mu, inv_res = 1.0 / (double)pp.res;
-  const double step = Ti * inv_res;
-  const double rT = 1.0 / Ti, rT2 = rT * rT;
-  const double wcm = pp.wc * pp.mu, wvm = pp.wv * pp.mu, wam = pp.wa * pp.mu;
+  const double rT = 1.0 / Ti;
+  const PieceScales k = piece_scales(pp, Ti, rT, inv_mu, inv_res);
+  const double K0 = k.step * k.wcm;  // (the rows are held divided by mu)
   double ct[3][D];  // c~
-  {
-    double tk = 1.0;
-#pragma unroll
-    for (int col = D - 1; col >= 0; --col) {
-#pragma unroll
-      for (int ax = 0; ax < 3; ++ax) ct[ax][col] = c[ax][col] * tk;
-      tk *= Ti;
-    }
-  }
+  normalised_coeffs<S>(c, Ti, ct);
   double gN[3][D];  // gradient w.r.t. c~
 #pragma unroll
   for (int ax = 0; ax < 3; ++ax)
 #pragma unroll
     for (int col = 0; col < D; ++col) gN[ax][col] = 0.0;
   double csum = 0.0, Rs1 = 0.0, Rs2 = 0.0;  // sum of the sample costs; Rs = (Rs1 + 2 Rs2) / T, see above
-  const double kv = rT * inv_mu, ka = rT2 * inv_mu, cv = pp.vmax * inv_mu, ca = pp.amax * inv_mu;
-  const double K1 = step * rT * pp.wv, K2 = step * rT2 * pp.wa;
   // Polytope rows are held in registers, RC at a time, and the sample loop runs inside: re-reading
   // them from L2 for every sample (res x M x 32 B per lane) was the bottleneck of this kernel.
   constexpr int RC = 8;
@@ -407,21 +358,14 @@ __device__ __forceinline__ void piece_penalty_part(const Penalty &pp_in, const d
         }
         a1[ax] = x1;
         a2[ax] = x2;
-        worst = fmax(worst, fmax(__builtin_fma(fabs(x1), kv, -cv), __builtin_fma(fabs(x2), ka, -ca)));
+        worst = fmax(worst, fmax(__builtin_fma(fabs(x1), k.kv, -k.cv), __builtin_fma(fabs(x2), k.ka, -k.ca)));
       }
       if (__any(worst > 0.0)) {
         double cost = 0.0;
 #pragma unroll
         for (int ax = 0; ax < 3; ++ax) {
-          double f, df;
-          smoothed_l1_unit(__builtin_fma(fabs(a1[ax]), kv, -cv), f, df);
-          cost = __builtin_fma(wvm, f, cost);
-          const double s1 = K1 * copysign(df, a1[ax]);
-          Rs1 = __builtin_fma(s1, a1[ax], Rs1);
-          smoothed_l1_unit(__builtin_fma(fabs(a2[ax]), ka, -ca), f, df);
-          cost = __builtin_fma(wam, f, cost);
-          const double s2 = K2 * copysign(df, a2[ax]);
-          Rs2 = __builtin_fma(s2, a2[ax], Rs2);
+          double s1, s2;
+          limit_terms(k, a1[ax], a2[ax], cost, Rs1, Rs2, s1, s2);
 #pragma unroll
           for (int col = 0; col < D; ++col)
             gN[ax][col] = __builtin_fma(s2, t2[col], __builtin_fma(s1, t1[col], gN[ax][col]));
@@ -499,17 +443,10 @@ __device__ __forceinline__ void piece_penalty_part(const Penalty &pp_in, const d
 #pragma unroll
       for (int r = 0; r < RC; ++r) {
         const double u = ur[r];
-        if (__any(u > 0.0)) {  // wave-uniform: inside the corridor nothing else is computed
-          const double w = fmax(u, 0.0), uc = fmin(w, 1.0), sq = uc * uc;
-          Fs += w - uc;
-          Fs = __builtin_fma(sq * uc, __builtin_fma(-0.5, uc, 1.0), Fs);
-          const double df = sq * __builtin_fma(-2.0, uc, 3.0);
-          G[0] = __builtin_fma(df, hr[r][0], G[0]);
-          G[1] = __builtin_fma(df, hr[r][1], G[1]);
-          G[2] = __builtin_fma(df, hr[r][2], G[2]);
-        }
+        if (__any(u > 0.0))  // wave-uniform: inside the corridor nothing else is computed
+          corridor_row_terms(u, hr[r], Fs, G[0], G[1], G[2]);
       }
-      double cost = wcm * Fs;
+      double cost = k.wcm * Fs;
       if (first) {
         // velocity / acceleration limits in units of mu, straight from the normalised-time sums a1 = sum c~ tab',
         // a2 = sum c~ tab'':  u = (|a1| / T - vmax) / mu = |a1| kv - cv  (one FMA, |.| is an operand modifier)
@@ -540,20 +477,13 @@ __device__ __forceinline__ void piece_penalty_part(const Penalty &pp_in, const d
           }
           a1[ax] = x1;
           a2[ax] = x2;
-          worst = fmax(worst, fmax(__builtin_fma(fabs(x1), kv, -cv), __builtin_fma(fabs(x2), ka, -ca)));
+          worst = fmax(worst, fmax(__builtin_fma(fabs(x1), k.kv, -k.cv), __builtin_fma(fabs(x2), k.ka, -k.ca)));
         }
-        if (__any(worst > 0.0)) {  // only one of +v, -v (+a, -a) can be violated: the slope has the sign of a1 (a2)
+        if (__any(worst > 0.0)) {
 #pragma unroll
           for (int ax = 0; ax < 3; ++ax) {
-            double f, df;
-            smoothed_l1_unit(__builtin_fma(fabs(a1[ax]), kv, -cv), f, df);
-            cost = __builtin_fma(wvm, f, cost);
-            const double s1 = K1 * copysign(df, a1[ax]);
-            Rs1 = __builtin_fma(s1, a1[ax], Rs1);
-            smoothed_l1_unit(__builtin_fma(fabs(a2[ax]), ka, -ca), f, df);
-            cost = __builtin_fma(wam, f, cost);
-            const double s2 = K2 * copysign(df, a2[ax]);
-            Rs2 = __builtin_fma(s2, a2[ax], Rs2);
+            double s1, s2;
+            limit_terms(k, a1[ax], a2[ax], cost, Rs1, Rs2, s1, s2);
             // (the gradient of the limit rows goes into gN here, while s1 and s2 are at hand)
 #pragma unroll
             for (int col = 0; col < D; ++col)
@@ -565,7 +495,7 @@ __device__ __forceinline__ void piece_penalty_part(const Penalty &pp_in, const d
         csum += cost;
 #pragma unroll
         for (int ax = 0; ax < 3; ++ax) {
-          const double s0 = step * wcm * G[ax];
+          const double s0 = K0 * G[ax];
 #pragma unroll
           for (int col = 0; col < D; ++col) gN[ax][col] = __builtin_fma(s0, t0[col], gN[ax][col]);
         }
@@ -573,25 +503,9 @@ __device__ __forceinline__ void piece_penalty_part(const Penalty &pp_in, const d
       if constexpr (!LTAB) nx.await();
     }
   }
-  pc = step * csum;
-  {  // d/dT at fixed c: the quadrature weight T/res and the sample times tau_j T
-    double acc = 0.0;
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax)
-#pragma unroll
-      for (int col = 0; col < D; ++col)
-        acc = __builtin_fma(ct[ax][col] * (double)(D - 1 - col), gN[ax][col], acc);
-    gT += csum * inv_res + rT * (acc - __builtin_fma(2.0, Rs2, Rs1));
-  }
-  {  // d/dc = T^k d/dc~
-    double tk = 1.0;
-#pragma unroll
-    for (int col = D - 1; col >= 0; --col) {
-#pragma unroll
-      for (int ax = 0; ax < 3; ++ax) gC[ax][col] = __builtin_fma(gN[ax][col], tk, gC[ax][col]);
-      tk *= Ti;
-    }
-  }
+  pc = k.step * csum;
+  gT += duration_grad(csum, inv_res, rT, sample_time_moment<S, D>(ct, gN), Rs1, Rs2);
+  add_coeff_grad<S>(gN, Ti, gC);
 }
 
 // The energy part of one (trajectory, piece) from its S highest-power coefficients ch: d/dc and d/dT of the piece's share of
@@ -1063,15 +977,6 @@ void with_minco_shape(int N, int c, F &&f) {
   if (N <= 4) f(MincoShape<4>{});
   else if (N <= 8) f(MincoShape<8>{});
   else f(MincoShape<16>{});
-}
-
-// The order ladder of the host launches: f(std::integral_constant<int, S>{}) with S = s for s = 2, 3 and S = 4 otherwise (the
-// callers have checked s)
-template <class F>
-decltype(auto) with_order(int s, F &&f) {
-  if (s == 2) return f(std::integral_constant<int, 2>{});
-  if (s == 3) return f(std::integral_constant<int, 3>{});
-  return f(std::integral_constant<int, 4>{});
 }
 
 }  // namespace anet

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "penalty_terms.h"  // smoothed_l1
 #include "lbfgs_kernels.h"
 #include "lbfgs_resident.h"
 

@@ -60,14 +60,11 @@ __device__ __forceinline__ void mx_column_set(const Penalty &pp, const double in
                                               const double Ti, const double (&cb)[3][2], Before &&before, After &&after,
                                               double (&gN)[3][2], double &csum, double &Rs1, double &Rs2, double &rT, double &step) {
   constexpr int NSL = kMxNSL;  // (RB: rows of a parked block, 16 or 8)
-  const double wcm = pp.wc * pp.mu, wvm = pp.wv * pp.mu, wam = pp.wa * pp.mu;
-  const double cv = pp.vmax * inv_mu, ca = pp.amax * inv_mu;
   rT = fast_rcp(Ti);
-  step = Ti * inv_res;
-  const double rT2 = rT * rT;
-  const double kv = rT * inv_mu, ka = rT2 * inv_mu;
+  const PieceScales k = piece_scales(pp, Ti, rT, inv_mu, inv_res);
+  step = k.step;
   const double thr1 = pp.vmax * Ti, thr2 = pp.amax * (Ti * Ti);
-  const double K0 = step * pp.wc, K1 = step * rT * pp.wv, K2 = step * rT2 * pp.wa;
+  const double K0 = k.step * pp.wc;  // (the normals are held as given, only the offsets divided by mu)
   // ---- forward, tiles 1 .. 3: velocity and acceleration of this lane's samples (and the position of its fifth) ----
   // Stage order (registers): limits -> their gradient steps u = 5 .. 14 -> position tile 0 -> corridor rows -> steps u = 0 .. 4;
   // a weight lives from its sample's penalty to its matrix instruction and no longer.
@@ -96,7 +93,7 @@ __device__ __forceinline__ void mx_column_set(const Penalty &pp, const double in
     }
   };
   csum = Rs1 = Rs2 = 0.0;
-  // ---- velocity / acceleration limits (the formulas of piece_penalty_part) ----
+  // ---- velocity / acceleration limits (penalty_terms.h) ----
 #pragma unroll
   for (int ii = 0; ii < NSL; ++ii) {
     double a1[3], a2[3];
@@ -107,20 +104,10 @@ __device__ __forceinline__ void mx_column_set(const Penalty &pp, const double in
     }
     // (|a1| kv - cv > 0 <=> |a1| > vmax T: two maxima and two compares instead of six FMAs and five maxima)
     const double m1 = fmax(fmax(fabs(a1[0]), fabs(a1[1])), fabs(a1[2])), m2 = fmax(fmax(fabs(a2[0]), fabs(a2[1])), fabs(a2[2]));
-    if (__any(m1 > thr1 || m2 > thr2)) {  // only one of +v, -v (+a, -a) can be violated: the slope has the sign of a1 (a2)
+    if (__any(m1 > thr1 || m2 > thr2)) {
       double cost = 0.0, s1[3], s2[3];
 #pragma unroll
-      for (int ax = 0; ax < 3; ++ax) {
-        double f, df;
-        smoothed_l1_unit(__builtin_fma(fabs(a1[ax]), kv, -cv), f, df);
-        cost = __builtin_fma(wvm, f, cost);
-        s1[ax] = K1 * copysign(df, a1[ax]);
-        Rs1 = __builtin_fma(s1[ax], a1[ax], Rs1);
-        smoothed_l1_unit(__builtin_fma(fabs(a2[ax]), ka, -ca), f, df);
-        cost = __builtin_fma(wam, f, cost);
-        s2[ax] = K2 * copysign(df, a2[ax]);
-        Rs2 = __builtin_fma(s2[ax], a2[ax], Rs2);
-      }
+      for (int ax = 0; ax < 3; ++ax) limit_terms(k, a1[ax], a2[ax], cost, Rs1, Rs2, s1[ax], s2[ax]);
       csum += cost;
       grad_step(NSL + ii, s1);
       grad_step(2 * NSL + ii, s2);
@@ -171,15 +158,8 @@ __device__ __forceinline__ void mx_column_set(const Penalty &pp, const double in
 #pragma unroll
         for (int ii = 0; ii < NSL; ++ii) {
           const double u = uq[ii];
-          if (__any(u > 0.0)) {  // wave-uniform: inside the corridor nothing else is computed
-            const double w = fmax(u, 0.0), uc = fmin(w, 1.0), sq = uc * uc;
-            Fs[ii] += w - uc;
-            Fs[ii] = __builtin_fma(sq * uc, __builtin_fma(-0.5, uc, 1.0), Fs[ii]);
-            const double df = sq * __builtin_fma(-2.0, uc, 3.0);
-            G[0][ii] = __builtin_fma(df, h[q][0], G[0][ii]);
-            G[1][ii] = __builtin_fma(df, h[q][1], G[1][ii]);
-            G[2][ii] = __builtin_fma(df, h[q][2], G[2][ii]);
-          }
+          if (__any(u > 0.0))  // wave-uniform: inside the corridor nothing else is computed
+            corridor_row_terms(u, h[q], Fs[ii], G[0][ii], G[1][ii], G[2][ii]);
         }
       }
     }
@@ -187,10 +167,70 @@ __device__ __forceinline__ void mx_column_set(const Penalty &pp, const double in
   }
 #pragma unroll
   for (int ii = 0; ii < NSL; ++ii) {
-    csum = __builtin_fma(wcm, Fs[ii], csum);
+    csum = __builtin_fma(k.wcm, Fs[ii], csum);
     if (__any(Fs[ii] > 0.0)) {  // (no violated row at this sample in the whole wave: its weights are zeros)
       const double w0[3] = {K0 * G[0][ii], K0 * G[1][ii], K0 * G[2][ii]};
       grad_step(ii, w0);
+    }
+  }
+}
+
+// What follows a column set, for the lane (r, .) of a pair: d/dT at fixed c and the pair's cost (the sums over the pair's four lanes
+// as products with a matrix of ones: every lane receives the sum), d/dc = T^k d/dc~ of the lane's two columns (g0, g1; t0, t1 their
+// powers of T, mx_column_powers) and, with_energy, the energy part as two more small products per axis: with
+// y_k = c_k' T^(S - 1 - k) = c~_k T^-S (k < S: the S highest powers, column k; a lane's own value) the gradient w.r.t. column i is
+// T^(S - i) sum_k E[i][k] y_k,  E[i][k] = 2 f_i f_k / (2 S - 1 - i - k),  f_k = (D - 1 - k)! / (S - 1 - k)!,  and d/dT =
+// (sum_k f_k y_k)^2 per axis: the A operands AE = E[i = lane & 3][k = lane >> 4] and AP = f_k of mx_energy_operands.
+template <int S>
+__device__ __forceinline__ void mx_energy_operands(const int lane, double &AE, double &AP) {
+  constexpr int D = 2 * S;
+  const int ie = lane & 3, ke = lane >> 4;
+  double fi = 1.0, fk = 1.0;
+  for (int e = 0; e < S; ++e) {
+    fi *= (double)(D - 1 - ie - e);
+    fk *= (double)(D - 1 - ke - e);
+  }
+  const bool in = ie < S && ke < S;
+  AE = in ? 2.0 * fi * fk / (double)(2 * S - 1 - ie - ke) : 0.0;
+  AP = ke < S ? fk : 0.0;
+}
+template <int D>
+__device__ __forceinline__ void mx_column_powers(const int r, const double (&tp)[D], double &t0, double &t1) {  // T^k of the columns r, 4 + r
+  t0 = mx_sel4(r, tp[D - 1], tp[D - 2], tp[D - 3], tp[D - 4]);
+  if constexpr (D == 8) t1 = mx_sel4(r, tp[3], tp[2], tp[1], tp[0]);
+  else t1 = mx_sel4(r, tp[1], tp[0], 0.0, 0.0);
+}
+template <int S>
+__device__ __forceinline__ void mx_pair_epilogue(const int r, const double (&cb)[3][2], const double (&gN)[3][2], const double csum,
+                                                 const double Rs1, const double Rs2, const double rT, const double step,
+                                                 const double inv_res, const double t0, const double t1, const bool with_energy,
+                                                 const double AE, const double AP, double (&g0)[3], double (&g1)[3], double &gT,
+                                                 double &pc) {
+  constexpr int D = 2 * S;
+  double acc = 0.0;
+#pragma unroll
+  for (int ax = 0; ax < 3; ++ax) {
+    acc = __builtin_fma(cb[ax][0] * (double)(D - 1 - r), gN[ax][0], acc);
+    acc = __builtin_fma(cb[ax][1] * (double)(D - 5 - r), gN[ax][1], acc);  // (cb = 0 where the column does not exist)
+  }
+  gT = __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, duration_grad(csum, inv_res, rT, acc, Rs1, Rs2), 0.0, 0, 0, 0);
+  pc = __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, step * csum, 0.0, 0, 0, 0);
+#pragma unroll
+  for (int ax = 0; ax < 3; ++ax) {
+    g0[ax] = gN[ax][0] * t0;
+    g1[ax] = gN[ax][1] * t1;
+  }
+  if (with_energy) {
+    // T^(S - r) = t0 T^-(S - 1)
+    const double rTS = S == 4 ? (rT * rT) * (rT * rT) : rT * (rT * rT);
+    const double TA = t0 * (S == 4 ? rT * (rT * rT) : rT * rT);
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+      const double ye = cb[ax][0] * rTS;
+      const double e = __builtin_amdgcn_mfma_f64_4x4x4f64(AE, ye, 0.0, 0, 0, 0);
+      const double ps = __builtin_amdgcn_mfma_f64_4x4x4f64(AP, ye, 0.0, 0, 0, 0);
+      g0[ax] = __builtin_fma(e, TA, g0[ax]);  // (e = 0 in the lanes r >= S)
+      gT = __builtin_fma(ps, ps, gT);
     }
   }
 }
@@ -232,21 +272,8 @@ __global__ void __launch_bounds__(256, ANET_PGMX_MINB) k_piece_grad_mx(PieceGrad
         lag[(u * 64 + lane) * 2 + ct] = tab[(size_t)(j * 4 + d) * D + (cc < D ? cc : 0)] * (cc < D ? 1.0 : 0.0);
       }
   }
-  // energy part as two more small products per axis: with y_k = c_k' T^(S - 1 - k) (k < S: the S highest powers, column k; a
-  // lane's own value) the gradient w.r.t. column i is  T^(S - i) sum_k E[i][k] y_k,  E[i][k] = 2 f_i f_k / (2 S - 1 - i - k),
-  // f_k = (D - 1 - k)! / (S - 1 - k)!, and d/dT = (sum_k f_k y_k)^2 per axis: A operands E[i = lane & 3][k = lane >> 4] and f_k
-  double AE, AP;
-  {
-    const int ie = lane & 3, ke = lane >> 4;
-    double fi = 1.0, fk = 1.0;
-    for (int e = 0; e < S; ++e) {
-      fi *= (double)(D - 1 - ie - e);
-      fk *= (double)(D - 1 - ke - e);
-    }
-    const bool in = ie < S && ke < S;
-    AE = in ? 2.0 * fi * fk / (double)(2 * S - 1 - ie - ke) : 0.0;
-    AP = ke < S ? fk : 0.0;
-  }
+  double AE, AP;  // (the energy part's A operands)
+  mx_energy_operands<S>(lane, AE, AP);
   __syncthreads();
   const int64_t b0 = ((int64_t)blockIdx.x * 4 + wave) * (16 * NCS);
   if (b0 >= a.B) return;
@@ -337,9 +364,7 @@ __global__ void __launch_bounds__(256, ANET_PGMX_MINB) k_piece_grad_mx(PieceGrad
 #pragma unroll
     for (int e = 1; e < D; ++e) tp[e] = tp[e - 1] * Ti;
     double tsel[2];
-    tsel[0] = mx_sel4(r, tp[D - 1], tp[D - 2], tp[D - 3], tp[D - 4]);
-    if constexpr (D == 8) tsel[1] = mx_sel4(r, tp[3], tp[2], tp[1], tp[0]);
-    else tsel[1] = mx_sel4(r, tp[1], tp[0], 0.0, 0.0);
+    mx_column_powers<D>(r, tp, tsel[0], tsel[1]);
     double cb[3][2];
 #pragma unroll
     for (int ax = 0; ax < 3; ++ax) {
@@ -363,36 +388,9 @@ __global__ void __launch_bounds__(256, ANET_PGMX_MINB) k_piece_grad_mx(PieceGrad
                        }
                      },
                      gN, csum, Rs1, Rs2, rT, step);
-    // ---- d/dT at fixed c (quadrature weight and sample times, as in piece_penalty_part); the sums over the pair's four lanes as
-    //      products with a matrix of ones (every lane receives the sum) ----
-    double acc = 0.0;
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-      acc = __builtin_fma(cb[ax][0] * (double)(D - 1 - r), gN[ax][0], acc);
-      acc = __builtin_fma(cb[ax][1] * (double)(D - 5 - r), gN[ax][1], acc);  // (cb = 0 where the column does not exist)
-    }
-    double gT = __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, csum * inv_res + rT * (acc - __builtin_fma(2.0, Rs2, Rs1)), 0.0, 0, 0, 0);
-    const double pc = __builtin_amdgcn_mfma_f64_4x4x4f64(1.0, step * csum, 0.0, 0, 0, 0);
-    // ---- d/dc = T^k d/dc~, the energy part, the stores ----
-    double g0[3], g1[3];
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-      g0[ax] = gN[ax][0] * tsel[0];
-      g1[ax] = gN[ax][1] * tsel[1];
-    }
-    if (a.with_energy) {
-      // y_k = c_k T^(S - 1 - k) = c~_k T^-S for the lane's column k = r < S (zero operands A elsewhere); T^(S - r) = tsel[0] T^-(S - 1)
-      const double rTS = S == 4 ? (rT * rT) * (rT * rT) : rT * (rT * rT);
-      const double TA = tsel[0] * (S == 4 ? rT * (rT * rT) : rT * rT);
-#pragma unroll
-      for (int ax = 0; ax < 3; ++ax) {
-        const double ye = cb[ax][0] * rTS;
-        const double e = __builtin_amdgcn_mfma_f64_4x4x4f64(AE, ye, 0.0, 0, 0, 0);
-        const double ps = __builtin_amdgcn_mfma_f64_4x4x4f64(AP, ye, 0.0, 0, 0, 0);
-        g0[ax] = __builtin_fma(e, TA, g0[ax]);  // (e = 0 in the lanes r >= S)
-        gT = __builtin_fma(ps, ps, gT);
-      }
-    }
+    // ---- d/dT, d/dc = T^k d/dc~, the energy part, the stores ----
+    double g0[3], g1[3], gT, pc;
+    mx_pair_epilogue<S>(r, cb, gN, csum, Rs1, Rs2, rT, step, inv_res, tsel[0], tsel[1], a.with_energy, AE, AP, g0, g1, gT, pc);
     if (live) {
       const int64_t lofs = rld + b;
 #pragma unroll

@@ -36,8 +36,7 @@
 #include <type_traits>
 
 #include "minco_core.h"  // fast_rcp
-#include "minco_kernels.h"  // pair_sum
-#include "wave_ops.h"  // wave_sum, wave_min_f64
+#include "wave_ops.h"  // wave_sum, wave_min_f64, pair_sum
 #include "qp_admm.h"    // qblk1, fallf
 
 namespace anet {

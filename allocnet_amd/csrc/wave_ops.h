@@ -94,6 +94,9 @@ __device__ __forceinline__ double half_max_nonneg(double v) {
 
 template <int CTRL>
 __device__ __forceinline__ double dpp_add(double v) { return v + dpp_f64<CTRL>(v); }
+// the lanes 2k, 2k+1 as a pair (quad_perm [1,0,3,2]): the other lane's value, and the sum of both
+__device__ __forceinline__ double lane_pair_swap(double v) { return dpp_f64<0xB1>(v); }
+__device__ __forceinline__ double pair_sum(double v) { return dpp_add<0xB1>(v); }
 // sum over the G adjacent lanes of a group (G = 4, 8, 16; every lane of the group ends with the total)
 template <int G>
 __device__ __forceinline__ double group_sum(double v) {
