@@ -18,6 +18,9 @@ from .min_traj_opt import MinTrajOpt, OsqpLayer  # noqa: F401
 from . import firi as _firi_mod  # noqa: F401
 from .firi import (firi, firi_dev, firi_params, convex_cover, polytope_depth, find_interior, overlap,  # noqa: F401
                    overlap_pt, short_cut, pack_model_inputs, to_planner_form)
+from . import polytope  # noqa: F401
+from .polytope import (polytope_vertices, polytope_vertices_dev, enumerate_vs, polytope_faces, polytope_volume,  # noqa: F401
+                       corridor_vertices)
 
 from . import voxel_map  # noqa: F401
 from .voxel_map import VoxelMap, gather_boxes_dev  # noqa: F401

@@ -89,6 +89,8 @@ PROTOTYPES = {
                               + [c_void_p] * 13),
     "anet_polytope_depth": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "anet_polytope_depth_dev": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "anet_polytope_vertices": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_double, c_int] + [c_void_p] * 4),
+    "anet_polytope_vertices_dev": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_double, c_int] + [c_void_p] * 5),
     "anet_firi_default_params": (None, [c_void_p]),
     "anet_firi": (c_int, [c_void_p, c_int64, c_int, c_int, c_int] + [c_void_p] * 10),
     "anet_firi_var": (c_int, [c_void_p, c_int64, c_int, c_int, c_int] + [c_void_p] * 11),

@@ -13,6 +13,7 @@
 //   api_voxel.hip      voxel map and route search
 //   api_flatness.hip   differential flatness: states, sampled limits, penalty gradients
 //   api_timenet.hip    the time-allocation network: weights handle, batched inference
+//   api_polytope.hip   vertex enumeration of polytopes (geo_utils::enumerateVs)
 //   piece_grad_unit.hip, qp_ipm_fuse_unit.hip: kernels scheduled for ILP, reached through launch functions
 // Only what two or more units use is here.  Nothing here is exported: the library's dynamic symbols stay the anet_* entry
 // points (and the kernels).

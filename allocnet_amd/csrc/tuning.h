@@ -63,12 +63,21 @@ struct Tuning {
   int ipm_split_steps = 4;
   // ANET_IPM_SPLIT_MIN_BATCH: smallest batch that takes two launches (520..560 problems lose 7-10 %, 600..1280 gain 10-19 %)
   PerCu ipm_split_min_batch{576, 0, -1};
+  // ---- vertex enumeration of polytopes (polytope_kernels.h)
+  // ANET_POLYTOPE_VERTICES_WAVE_MIN_BATCH, ANET_POLYTOPE_VERTICES_WAVE_MAX_ROWS: one wave per polytope from this batch on when
+  // max_rows is at most that many, else the workgroup's four waves per polytope.  Measured (one run): 131 072 x 16
+  // rows 0.823 ms against 0.879, but 8 192 x 64 rows 8.95 ms against 8.11 (a wave's 6 KB kept list halves the residency there) and
+  // one plan's 21 polytopes 0.452 against 0.320; 32 rows and 1024 polytopes (four per compute unit) lie between the measured points
+  PerCu polytope_vertices_wave_min_batch{1024, 0, -1};
+  int polytope_vertices_wave_max_rows = 32;
 
   // ---- per call (env_set at every use: tests set and unset them inside one process)
   // ANET_MVIE_STATE_IN_MEMORY: the MVIE L-BFGS with its state in memory (k_lbfgs_mvie_persistent), not in registers
   static constexpr const char *mvie_state_in_memory = "ANET_MVIE_STATE_IN_MEMORY";
   // ANET_POLYTOPE_DEPTH_ENUMERATE: polytope depths by vertex enumeration only, without the certified ascent in front
   static constexpr const char *polytope_depth_enumerate = "ANET_POLYTOPE_DEPTH_ENUMERATE";
+  // ANET_POLYTOPE_VERTICES_WPP: 1 or 4 waves per polytope in k_polytope_vertices whatever the batch (the results are the same bits)
+  static constexpr const char *polytope_vertices_wpp = "ANET_POLYTOPE_VERTICES_WPP";
 };
 
 // a per-call switch: set (to anything) or not
@@ -100,6 +109,8 @@ inline const Tuning &tuning() {
     env_override("ANET_IPM_THREE_PER_CU_MIN_BATCH", v.ipm_three_per_cu_min_batch.env);
     env_override("ANET_IPM_SPLIT_STEPS", v.ipm_split_steps);
     env_override("ANET_IPM_SPLIT_MIN_BATCH", v.ipm_split_min_batch.env);
+    env_override("ANET_POLYTOPE_VERTICES_WAVE_MIN_BATCH", v.polytope_vertices_wave_min_batch.env);
+    env_override("ANET_POLYTOPE_VERTICES_WAVE_MAX_ROWS", v.polytope_vertices_wave_max_rows);
     return v;
   }();
   return t;

@@ -518,6 +518,34 @@ int anet_polytope_depth(anet_ctx *ctx, int64_t batch, int max_rows, const double
 int anet_polytope_depth_dev(anet_ctx *ctx, int64_t batch, int max_rows, const double *hpoly, int normalise,
                             double *depth, double *point, void *stream);
 
+/* geo_utils::enumerateVs (geo_utils.hpp:155-202, with filterVs :128-150), batched: the vertices of polytopes given by their
+ * half-spaces, hpoly as for anet_polytope_depth (all-zero rows are padding), 1 <= max_rows <= 128 (two stacked FIRI outputs;
+ * ANET_ERR_UNSUPPORTED beyond).  The rows are scaled to unit normals (n, d).  A triple i < j < k of them with
+ * |det(n_i, n_j, n_k)| >= 1e-8 gives a candidate point; it is feasible when n.x + d <= epsilon for every row (epsilon: the
+ * reference's parameter, 1e-6 there).  Feasible candidates are visited in ascending lexicographic order of (i, j, k) and one is
+ * dropped when a vertex kept before it lies within max(epsilon, mag * DBL_EPSILON) of it in the max-norm (mag: the largest
+ * absolute coordinate among the kept vertices and the candidate) -- filterVs's resolution as a distance, where the reference
+ * rounds to a grid and compares cells (two points 1e-12 apart on both sides of a cell edge stay distinct there).  verts[b] holds
+ * the kept vertices in that order, whatever the launch shape.
+ * active (or NULL): per kept vertex the rows with |n.x + d| <= epsilon, bit r % 64 of word r / 64 for row r of hpoly[b].
+ * status[b] (or NULL): ANET_POLYTOPE_OK; ANET_POLYTOPE_SKIPPED with count[b] = 0 when the polytope's depth
+ * (anet_polytope_depth, normalised) is not a positive finite number -- empty, flat, padding only, or unbounded: where the
+ * reference's two-argument overload returns false -- or when no triple gives a feasible point (a slab: an unbounded set of
+ * finite depth; an unbounded polytope that HAS vertices is not detected, corridors carry their bounding box);
+ * ANET_POLYTOPE_TRUNCATED when it has more vertices than max_vertices (>= 1): count[b] is the true number, the first
+ * max_vertices are written -- or more than 256 distinct ones: count[b] = 256, a lower bound (252 = 2 * rows - 4 is the most a
+ * polytope of 128 rows has; 2 * rows - 4 vertices suffice for every non-degenerate polytope).
+ * The host call zero-fills the slots behind count[b]; the _dev call leaves them as they are, takes device pointers, runs
+ * asynchronously on `stream` and keeps the depths in the context's workspace (calls on one context do not overlap).        */
+#define ANET_POLYTOPE_OK 0
+#define ANET_POLYTOPE_SKIPPED 1
+#define ANET_POLYTOPE_TRUNCATED 2
+int anet_polytope_vertices(anet_ctx *ctx, int64_t batch, int max_rows, const double *hpoly, double epsilon, int max_vertices,
+                           double *verts /* [batch][max_vertices][3] */, int32_t *count /* [batch] */,
+                           uint64_t *active /* [batch][max_vertices][2] or NULL */, int32_t *status /* [batch] or NULL */);
+int anet_polytope_vertices_dev(anet_ctx *ctx, int64_t batch, int max_rows, const double *hpoly, double epsilon, int max_vertices,
+                               double *verts, int32_t *count, uint64_t *active, int32_t *status, void *stream);
+
 /* ---- batched L-BFGS ------------------------------------------------------------------------ */
 /* lbfgs::lbfgs_parameter_t, same fields and defaults (gcopter/lbfgs.hpp:15-129). */
 typedef struct anet_lbfgs_params {

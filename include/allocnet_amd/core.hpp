@@ -119,6 +119,10 @@ struct MatrixX {
   std::vector<double> a;
   MatrixX() = default;
   MatrixX(int r, int c) : r_(r), c_(c), a((size_t)r * c, 0.0) {}
+  void resize(int r, int c) {  // (contents are not kept, as with Eigen's resize to another size)
+    r_ = r; c_ = c;
+    a.assign((size_t)r * c, 0.0);
+  }
   double &operator()(int r, int c) { return a[(size_t)r * c_ + c]; }
   double operator()(int r, int c) const { return a[(size_t)r * c_ + c]; }
   int rows() const { return r_; }
