@@ -13,7 +13,7 @@ from .lbfgs import (lbfgs_parameter_t, lbfgs_strerror, lbfgs_mvie, lbfgs_minco, 
                     launch_order_from_counts, lbfgs_optimize_dev, lbfgs_optimize)
 from . import qp  # noqa: F401
 from .qp import (qp_assemble, qp_dims, qp_solve, qp_solve_vjp, qp_solve_dev, qp_solve_vjp_dev, qp_settings,  # noqa: F401
-                 QPSolver, QPConfig)
+                 qp_ipm_launch_form, QPSolver, QPConfig)
 from .min_traj_opt import MinTrajOpt, OsqpLayer  # noqa: F401
 from . import firi as _firi_mod  # noqa: F401
 from .firi import (firi, firi_dev, firi_params, convex_cover, polytope_depth, find_interior, overlap,  # noqa: F401

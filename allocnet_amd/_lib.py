@@ -77,6 +77,7 @@ PROTOTYPES = {
     "anet_qp_solve_workspace": (c_int64, [c_int, c_int, c_int64, c_int, c_int]),
     "anet_qp_solve_dev": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_int, c_double, c_double, c_double]
                           + [c_void_p] * 11),
+    "anet_qp_ipm_launch_form": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_int, c_int]),
     "anet_qp_solve_ordered_dev": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_int, c_double, c_double, c_double]
                                   + [c_void_p] * 12),
     "anet_qp_solve_time_grad": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_int, c_double, c_double, c_double]

@@ -148,6 +148,63 @@ __global__ void k_qp_mark_not_run(int64_t B, int *status, int *iters, double *ob
   obj[b] = __builtin_nan("");
 }
 
+// The LDS of one interior-point workgroup; the shape is the caller's to check
+static size_t qp_ipm_lds(int s, int n_pieces, int res, int M) {
+  return (s == 4) ? anet::qp_ipm_lds_bytes<4>(n_pieces, res, M) : anet::qp_ipm_lds_bytes<3>(n_pieces, res, M);
+}
+
+// Which form of the interior point a batch takes on this context's device (ANET_QP_IPM_FORM_*: the workgroups per CU the kernel's
+// registers are bounded for, | THROUGHPUT, | TWO_LAUNCHES): the ONE statement of the selection -- qp_solve_dev_impl launches by
+// it, anet_qp_ipm_launch_form reports it.  max_iter is the step limit of the solve (after its cap at 200).  Negative = error
+// (bad shape, or a problem that does not fit the LDS); no error text is set here, the callers have their own.
+static int qp_ipm_launch_form(anet_ctx *ctx, int s, int n_pieces, int64_t batch, int res, int M, bool has_launch_order,
+                              int max_iter) {
+  if (!ctx || (s != 3 && s != 4) || n_pieces < 1 || batch < 0 || res < 1 || M < 0) return ANET_ERR_INVALID;
+  const size_t ldsb = qp_ipm_lds(s, n_pieces, res, M);
+  if (ldsb > 160 * 1024) return ANET_ERR_UNSUPPORTED;
+  if (batch == 0) return 0;
+  const anet::Tuning &t = anet::tuning();
+  // two workgroups per CU (registers bounded to 256) from this batch on, when two fit the LDS: more than two rounds of one
+  // workgroup per CU (measured on 256 CUs): below that a batch lasts as long as its slowest problem and a problem alone on its
+  // CU is faster (512 problems are a draw -- 2.86 / 1.88 / 2.95 ms against 2.64 / 1.63 / 3.42 ms for 8 snap / 5 jerk / 5 snap
+  // pieces --, 768 problems gain 15-20 % from two per CU, 320 lose 15 %)
+  const bool two_per_cu = batch >= t.ipm_two_per_cu_min_batch.at(ctx->cus) && 2 * ldsb <= 160 * 1024;
+  // Shapes that put two workgroups on a CU visit the rows once more per step instead of carrying the next step's sums
+  // through the updating pass (registers: qp_ipm.h FUSE); a lone problem, a small batch or a problem whose LDS fills the
+  // CU takes the fused form.  (jerk: the unbounded instantiation needs <= 256 registers as it is -- two workgroups per CU
+  // -- and the compiler schedules it for latency; bounded to 256 it is 18 % slower per problem at the same occupancy)
+  if (!two_per_cu) return 1;  // (qp_ipm_fuse_unit.hip: the FUSE instantiations, scheduled for ILP)
+  // ... and THREE for jerk problems whose LDS allows it, from a batch on that fills them several times over (registers bounded
+  // to 168: 464 B of scratch).  Measured (round 5, same box, 5 jerk pieces): 4096 problems 3.96-4.00 -> 3.77-3.85 ms; 3000:
+  // 3.02-3.07 -> 3.21-3.25; 2048: 2.09-2.12 -> 2.42-2.43 (1024: 1.60 -> 1.91 in round 4) -- selected by batch like every other
+  // shape here (ANET_IPM_THREE_PER_CU_MIN_BATCH overrides; 0 disables)
+  const int64_t ipm_three_per_cu_min_batch = t.ipm_three_per_cu_min_batch.at(ctx->cus);
+  const bool three_per_cu = s == 3 && ipm_three_per_cu_min_batch > 0 && batch >= ipm_three_per_cu_min_batch && 3 * ldsb <= 160 * 1024;
+  // the shape of large batches: four row passes, registers bounded for 2 (snap) or 3 per CU (jerk: 1 where three do not apply)
+  int form = ANET_QP_IPM_FORM_THROUGHPUT | (s == 4 ? 2 : three_per_cu ? 3 : 1);
+  // Large batches in TWO launches (qp_ipm.h, IpmArgs::it_stop): the first takes every problem through the same number of Newton
+  // steps -- no tail: all workgroups are equally long --, the second resumes the unfinished ones longest-expected first.  A batch
+  // of 4096 in one launch ends 27 % above its balanced figure because its 30..50-step problems start whenever their turn comes.
+  // (from 576 problems on 256 CUs: 520..560 problems lose 7-10 %, 600..1280 gain 10-19 %)
+  if (t.ipm_split_steps > 0 && batch >= t.ipm_split_min_batch.at(ctx->cus) && !has_launch_order && max_iter > t.ipm_split_steps)
+    form |= ANET_QP_IPM_FORM_TWO_LAUNCHES;
+  return form;
+}
+
+// the step limit of an interior-point solve with these settings
+static int qp_ipm_max_iter(const anet_qp_settings &st) { return st.max_iter < 200 ? st.max_iter : 200; }
+
+int anet_qp_ipm_launch_form(anet_ctx *ctx, int s, int n_pieces, int64_t batch, int res, int M, int with_launch_order) {
+  if (!ctx) return fail(nullptr, ANET_ERR_INVALID, "ctx is NULL");
+  anet_qp_settings st_;
+  anet_qp_default_settings(&st_);
+  const int form = qp_ipm_launch_form(ctx, s, n_pieces, batch, res, M, with_launch_order != 0, qp_ipm_max_iter(st_));
+  if (form == ANET_ERR_UNSUPPORTED)
+    return fail(ctx, form, "anet_qp_ipm_launch_form: problem too large for the 160 KB LDS (interior-point method)");
+  if (form < 0) return fail(ctx, form, "anet_qp_ipm_launch_form: bad shape");
+  return form;
+}
+
 static int qp_solve_dev_impl(anet_ctx *ctx, int s, int n_pieces, int64_t batch, int res, int M, double max_vel,
                              double max_acc, double m34, const double *state, const double *T,
                              const double *hpolys, const anet_qp_settings *settings, double *work, double *coeffs,
@@ -169,7 +226,7 @@ static int qp_solve_dev_impl(anet_ctx *ctx, int s, int n_pieces, int64_t batch, 
   if (st_.method != ANET_QP_METHOD_ADMM && st_.method != ANET_QP_METHOD_INTERIOR_POINT)
     return fail(ctx, ANET_ERR_INVALID, "anet_qp_solve: unknown method");
   if (st_.method == ANET_QP_METHOD_INTERIOR_POINT) {
-    const size_t ldsb = (s == 4) ? anet::qp_ipm_lds_bytes<4>(n_pieces, res, M) : anet::qp_ipm_lds_bytes<3>(n_pieces, res, M);
+    const size_t ldsb = qp_ipm_lds(s, n_pieces, res, M);
     if (ldsb > 160 * 1024)
       return fail(ctx, ANET_ERR_UNSUPPORTED, "anet_qp_solve: problem too large for the 160 KB LDS (interior-point method)");
     const int64_t mi = (int64_t)n_pieces * res * (M + 12);
@@ -182,7 +239,7 @@ static int qp_solve_dev_impl(anet_ctx *ctx, int s, int n_pieces, int64_t batch, 
     if (grad_z && tol > 1e-9) tol = 1e-9;
     anet::IpmArgs ia{state, T, hpolys, work, work + mi * batch, coeffs, obj, status, iters,
                      residuals ? residuals : work + 2 * mi * batch, grad_T, grad_z, vjp_T, batch, n_pieces, res, M, max_vel,
-                     max_acc, m34, tol, st_.max_iter < 200 ? st_.max_iter : 200, tol_plain > tol ? tol_plain : 0.0, 0.1 * tol, 0, launch_order, 0, 0, nullptr, nullptr};
+                     max_acc, m34, tol, qp_ipm_max_iter(st_), tol_plain > tol ? tol_plain : 0.0, 0.1 * tol, 0, launch_order, 0, 0, nullptr, nullptr};
     const anet::Tuning &t = anet::tuning();
     ia.twist_min_pieces = t.ipm_twist_min_pieces;
     hipStream_t sti = (hipStream_t)stream;
@@ -237,40 +294,25 @@ static int qp_solve_dev_impl(anet_ctx *ctx, int s, int n_pieces, int64_t batch, 
       }
     } prof_dump{ctx, d_iprof, sti};
 #endif
-    // two workgroups per CU (registers bounded to 256) from this batch on, when two fit the LDS: more than two rounds of one
-    // workgroup per CU (measured on 256 CUs): below that a batch lasts as long as its slowest problem and a problem alone on its
-    // CU is faster (512 problems are a draw -- 2.86 / 1.88 / 2.95 ms against 2.64 / 1.63 / 3.42 ms for 8 snap / 5 jerk / 5 snap
-    // pieces --, 768 problems gain 15-20 % from two per CU, 320 lose 15 %)
-    const bool two_per_cu = batch >= t.ipm_two_per_cu_min_batch.at(ctx->cus) && 2 * ldsb <= 160 * 1024;
-    // ... and THREE for jerk problems whose LDS allows it, from a batch on that fills them several times over (registers bounded
-    // to 168: 464 B of scratch).  Measured (round 5, same box, 5 jerk pieces): 4096 problems 3.96-4.00 -> 3.77-3.85 ms; 3000:
-    // 3.02-3.07 -> 3.21-3.25; 2048: 2.09-2.12 -> 2.42-2.43 (1024: 1.60 -> 1.91 in round 4) -- selected by batch like every other
-    // shape here (ANET_IPM_THREE_PER_CU_MIN_BATCH overrides; 0 disables)
-    const int64_t ipm_three_per_cu_min_batch = t.ipm_three_per_cu_min_batch.at(ctx->cus);
-    const bool three_per_cu = s == 3 && two_per_cu && ipm_three_per_cu_min_batch > 0 && batch >= ipm_three_per_cu_min_batch &&
-                              3 * ldsb <= 160 * 1024;
+    const int form = qp_ipm_launch_form(ctx, s, n_pieces, batch, res, M, launch_order != nullptr, ia.max_iter);
+    if (form < 0) return fail(ctx, form, "anet_qp_solve: no interior-point form for this shape");
     auto launch_ipm = [&](auto kern) -> int {
       ANET_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
       hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(256), ldsb, sti, ia);
       return ANET_OK;
     };
-    auto launch_throughput = [&]() -> int {  // the shape of large batches: four row passes, registers bounded for 2 or 3 per CU
+    auto launch_throughput = [&]() -> int {
       if (s == 4) return launch_ipm(anet::k_qp_ipm<4, 2, false>);
-      return three_per_cu ? launch_ipm(anet::k_qp_ipm<3, 3, false>) : launch_ipm(anet::k_qp_ipm<3, 1, false>);
+      return (form & ANET_QP_IPM_FORM_PER_CU_MASK) == 3 ? launch_ipm(anet::k_qp_ipm<3, 3, false>) : launch_ipm(anet::k_qp_ipm<3, 1, false>);
     };
     int rc_l;
-    // Large batches in TWO launches (qp_ipm.h, IpmArgs::it_stop): the first takes every problem through the same number of Newton
-    // steps -- no tail: all workgroups are equally long --, the second resumes the unfinished ones longest-expected first.  A batch
-    // of 4096 in one launch ends 27 % above its balanced figure because its 30..50-step problems start whenever their turn comes.
-    // (from 576 problems on 256 CUs: 520..560 problems lose 7-10 %, 600..1280 gain 10-19 %)
-    const int split_steps = t.ipm_split_steps;
-    if (two_per_cu && split_steps > 0 && batch >= t.ipm_split_min_batch.at(ctx->cus) && !launch_order && ia.max_iter > split_steps) {
+    if (form & ANET_QP_IPM_FORM_TWO_LAUNCHES) {
       const int ny = 3 * s * (n_pieces + 1);
       const int64_t m_adm = 3 * (6 + (int64_t)s * (n_pieces - 1)) + mi;
       ResumeTail rt{qp_cont_doubles(s, n_pieces), batch};
       rt.carve(work + 2 * m_adm * batch + 2 * batch);
       ia.cont = rt.cont;
-      ia.it_stop = split_steps;
+      ia.it_stop = t.ipm_split_steps;
       rc_l = launch_throughput();
       if (rc_l != ANET_OK) return rc_l;
       rc_l = resume_parked(
@@ -289,11 +331,7 @@ static int qp_solve_dev_impl(anet_ctx *ctx, int s, int n_pieces, int64_t batch, 
       ANET_HIP(ctx, hipGetLastError());
       return ANET_OK;
     }
-    // Shapes that put two workgroups on a CU visit the rows once more per step instead of carrying the next step's sums
-    // through the updating pass (registers: qp_ipm.h FUSE); a lone problem, a small batch or a problem whose LDS fills the
-    // CU takes the fused form.  (jerk: the unbounded instantiation needs <= 256 registers as it is -- two workgroups per CU
-    // -- and the compiler schedules it for latency; bounded to 256 it is 18 % slower per problem at the same occupancy)
-    if (!two_per_cu) {  // (qp_ipm_fuse_unit.hip: the FUSE instantiations, scheduled for ILP)
+    if (!(form & ANET_QP_IPM_FORM_THROUGHPUT)) {
       ANET_HIP(ctx, (hipError_t)anet::launch_qp_ipm_fuse(s, batch, ldsb, sti, ia));
       rc_l = ANET_OK;
     } else rc_l = launch_throughput();

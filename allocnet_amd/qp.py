@@ -145,6 +145,23 @@ def qp_solve_vjp(order, iniPVA, finPVA, hPolys, times, grad_z, res=20, max_vel=4
     return dict(coeffs=coeffs, obj=obj, status=status, iters=iters, residuals=resid, grad_T=gT)
 
 
+IPM_FORM_PER_CU_MASK = 0x3      # ANET_QP_IPM_FORM_*: the bits of qp_ipm_launch_form
+IPM_FORM_THROUGHPUT = 0x10
+IPM_FORM_TWO_LAUNCHES = 0x20
+
+
+def qp_ipm_launch_form(order, N, B, res=20, M=16, with_launch_order=False, ctx=None):
+    """anet_qp_ipm_launch_form: the form of the interior-point kernel a batch of B problems (N pieces, res samples per piece, M
+    corridor rows per piece) takes on this context's device with the default settings -- form & IPM_FORM_PER_CU_MASK the
+    workgroups per compute unit the kernel is bounded for (1, 2 or 3), IPM_FORM_THROUGHPUT set for the four-pass form of large
+    batches (clear: the FUSE form), IPM_FORM_TWO_LAUNCHES set when the batch runs in two launches; 0 for an empty batch."""
+    ctx = ctx or default_context(0)
+    n = ctx.lib.anet_qp_ipm_launch_form(ctx.handle, int(order), int(N), int(B), int(res), int(M), int(bool(with_launch_order)))
+    if n < 0:
+        ctx.check(n)
+    return n
+
+
 def _qp_dev_common(order, state, times, hPolys, res, ctx):
     import torch
     if not (state.is_cuda and times.is_cuda and hPolys.is_cuda):

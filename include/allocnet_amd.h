@@ -447,6 +447,20 @@ int anet_qp_solve_dev(anet_ctx *ctx, int s, int n_pieces, int64_t batch, int res
                       const double *hpolys, const anet_qp_settings *settings, double *work, double *coeffs,
                       double *obj, int32_t *status, int32_t *iters, double *residuals, void *stream);
 
+/* The form of the interior-point kernel a batch of this shape takes on this context's device with the default settings (the
+ * selection of anet_qp_solve* itself: allocnet_amd/csrc/api_qp.hip), as a bit set:
+ *   form & ANET_QP_IPM_FORM_PER_CU_MASK   workgroups per compute unit the kernel's registers are bounded for: 1, 2 or 3
+ *   form & ANET_QP_IPM_FORM_THROUGHPUT    the four-pass form of large batches; clear = the FUSE form (small batches, lone problems,
+ *                                         problems whose LDS fills a compute unit; always 1 per compute unit)
+ *   form & ANET_QP_IPM_FORM_TWO_LAUNCHES  every problem through a few Newton steps, then the unfinished ones resumed
+ * with_launch_order != 0: as for anet_qp_solve_ordered_dev with an order (always one launch).  0 for an empty batch (nothing
+ * is launched); negative = error: ANET_ERR_INVALID (bad shape), ANET_ERR_UNSUPPORTED (the problem does not fit the 160 KB LDS).
+ * For tests and callers that label a measurement with the kernel that ran.                                                  */
+#define ANET_QP_IPM_FORM_PER_CU_MASK 0x3
+#define ANET_QP_IPM_FORM_THROUGHPUT 0x10
+#define ANET_QP_IPM_FORM_TWO_LAUNCHES 0x20
+int anet_qp_ipm_launch_form(anet_ctx *ctx, int s, int n_pieces, int64_t batch, int res, int M, int with_launch_order);
+
 /* The same with a launch order for the interior-point method (one workgroup per problem, 512 resident at a time: a batch ends
  * with whichever long problem started late -- 27 % above its balanced figure for 4096 problems): launch_order
  * (device, int32 [batch], a permutation of 0..batch-1) is the problem each successive workgroup takes; longest first from the
