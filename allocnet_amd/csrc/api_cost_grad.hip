@@ -154,18 +154,13 @@ int cost_grad_dev_impl(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batch,
       return ANET_OK;
     }
   }
-  const int64_t nco = (int64_t)n_pieces * 3 * 2 * s;
-  double *w_co = coeffs_out ? coeffs_out : work;
-  double *w_gdC = work + nco * ld;
-  double *w_gdT = w_gdC + nco * ld;
-  double *w_pc = w_gdT + (int64_t)n_pieces * ld;
-  double *w_en = w_pc + (int64_t)n_pieces * ld;
-  rc = anet_minco_solve_dev(ctx, s, c, n_pieces, batch, ld, head, tail, wps, T, w_co, w_en, stream);
+  const anet::CostGradWs W = anet::cost_grad_ws(work, s, n_pieces, ld);
+  double *w_co = coeffs_out ? coeffs_out : W.co;
+  rc = anet_minco_solve_dev(ctx, s, c, n_pieces, batch, ld, head, tail, wps, T, w_co, W.en, stream);
   if (rc) return rc;
-  rc = anet_minco_partial_grads_dev(ctx, s, n_pieces, batch, ld, w_co, T, hpolys, pen, 1, w_gdC, w_gdT,
-                                    w_pc, stream);
+  rc = anet_minco_partial_grads_dev(ctx, s, n_pieces, batch, ld, w_co, T, hpolys, pen, 1, W.gdC, W.gdT, W.pc, stream);
   if (rc) return rc;
-  anet::PropArgs a{T, w_co, w_gdC, w_gdT, gradP, gradT, w_en, pen ? w_pc : nullptr, cost,
+  anet::PropArgs a{T, w_co, W.gdC, W.gdT, gradP, gradT, W.en, pen ? W.pc : nullptr, cost,
                    pen ? pen->rho : 0.0, batch, ld, n_pieces, c, tau};
   return do_propagate(ctx, s, a, (hipStream_t)stream);
 }
@@ -229,8 +224,7 @@ int anet_minco_propagate_grad_dev(anet_ctx *ctx, int s, int c, int n_pieces, int
 }
 
 int64_t anet_minco_cost_grad_workspace(int s, int n_pieces, int64_t ld) {
-  // coeffs + gdC + gdT + piece cost + energy
-  return ((int64_t)n_pieces * 3 * 2 * s * 2 + 2 * (int64_t)n_pieces + 1) * ld;
+  return anet::cost_grad_ws(nullptr, s, n_pieces, ld).doubles;
 }
 
 int anet_minco_cost_grad_launches(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batch, const anet_penalty *pen) {

@@ -27,6 +27,7 @@
 
 #include "../../include/allocnet_amd.h"
 #include "tuning.h"
+#include "workspace.h"  // the shape of every workspace and staging buffer: the only place one is written
 
 #pragma GCC visibility push(hidden)
 
@@ -128,6 +129,15 @@ inline int ensure_scratch(anet_ctx *ctx, size_t bytes) {
   }
   ctx->scratch_bytes = bytes;
   return ANET_OK;
+}
+
+// The scratch of a host (trajectory-major) entry point: layout(base) runs an anet::Cursor over base and returns the bytes taken --
+// once on nullptr to size the scratch, once on the scratch to set the caller's pointers.
+template <class Layout>
+int stage_scratch(anet_ctx *ctx, Layout &&layout) {
+  const int rc = ensure_scratch(ctx, (size_t)layout(nullptr));
+  if (rc == ANET_OK) (void)layout(ctx->scratch);
+  return rc;
 }
 
 inline int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
@@ -265,36 +275,15 @@ inline int make_stager(anet_ctx *ctx, int64_t batch, int64_t max_field, int64_t 
   return ANET_OK;
 }
 
-// Launch order for anet_lbfgs_minco_ordered_dev from the evaluation counts of a previous solve: a counting sort into 4096
-// buckets of 16 evaluations, longest first (the order inside a bucket is whatever the atomics make it: irrelevant here).
-constexpr int kOrderBuckets = 4096;
-
-// the counting sort of the launch order (api_lbfgs.hip): shift 4 for evaluation counts, 0 for Newton-step counts
+// the counting sort of the launch order (api_lbfgs.hip; anet::kOrderBuckets buckets, longest first): shift 4 for evaluation counts, 0 for Newton-step counts
 int launch_order_impl(anet_ctx *ctx, int64_t batch, const int32_t *counts, int32_t *launch_order, int32_t *work, void *stream,
                       int shift);
-
-// The tail of the workspace of a solve that can run in two launches (the one-launch L-BFGS, the interior-point QP): the parked
-// state of every problem (`per` doubles each), then its score and the order of the second launch (int32 rows of ld, each padded
-// to whole doubles) and the bins of the counting sort.  doubles() is what the _workspace functions add for it, carve() is how
-// the _dev_impls cut it.
-struct ResumeTail {
-  int64_t per, ld;
-  double *cont;
-  int32_t *score, *order, *bins;
-  static int64_t doubles(int64_t per, int64_t ld) { return per * ld + ld + 2 + kOrderBuckets / 2; }
-  void carve(double *w) {
-    cont = w;
-    score = (int32_t *)(cont + per * ld);
-    order = score + ld + (ld & 1);
-    bins = order + ld + (ld & 1);
-  }
-};
 
 // Between the two launches of a two-launch solve, whose first launch parked the unfinished problems in t.cont: score them
 // (score(t.score) enqueues the solver's score kernel), counting-sort the scores into the order of the second launch, longest-
 // expected first, and enqueue that launch (resume(t.order)).
 template <class Score, class Resume>
-int resume_parked(anet_ctx *ctx, int64_t batch, const ResumeTail &t, hipStream_t st, Score &&score, Resume &&resume) {
+int resume_parked(anet_ctx *ctx, int64_t batch, const anet::ResumeTail &t, hipStream_t st, Score &&score, Resume &&resume) {
   score(t.score);
   const int rc = launch_order_impl(ctx, batch, t.score, t.order, t.bins, st, 0);
   return rc ? rc : resume(t.order);

@@ -14,40 +14,25 @@ static anet::LbfgsP to_kernel_params(const anet_lbfgs_params &p) {
                       p.min_step, p.max_step, p.f_dec_coeff, p.s_curv_coeff, p.cautious_factor, p.machine_prec};
 }
 
-struct LbfgsLayout {
-  int n, m, npf;
-  int64_t ld;
-  double *x, *g, *xp, *gp, *d, *lm_s, *lm_y, *lm_ys, *lm_alpha, *pf, *ds, *feval;
-  int *is;
-  static int64_t doubles(int n, int m, int npf, int64_t ld) {
-    // + IS_COUNT_ int32 rows, rounded up to doubles
-    return ((int64_t)n * (5 + 2 * m) + 2 * m + npf + anet::DS_COUNT_ + 1 + (anet::IS_COUNT_ + 1) / 2) * ld;
-  }
-  void carve(double *w) {
-    x = w; g = x + (int64_t)n * ld; xp = g + (int64_t)n * ld; gp = xp + (int64_t)n * ld; d = gp + (int64_t)n * ld;
-    lm_s = d + (int64_t)n * ld; lm_y = lm_s + (int64_t)m * n * ld; lm_ys = lm_y + (int64_t)m * n * ld;
-    lm_alpha = lm_ys + (int64_t)m * ld; pf = lm_alpha + (int64_t)m * ld; ds = pf + (int64_t)npf * ld;
-    feval = ds + (int64_t)anet::DS_COUNT_ * ld; is = (int *)(feval + ld);
-  }
-  // The kernels' view of this layout for B problems.  wave: the internal vectors (xp, gp, d, lm_s, lm_y) problem-major (element i
-  // of problem b at [i + b*n]: one wave per problem), else batch-minor (one lane per problem).  What a call site has beyond
-  // this -- variable map, step bound, cancel word, host callbacks -- it sets by field name.
-  anet::LbfgsArgs args(int64_t B, const anet_lbfgs_params &p, bool wave) const {
-    anet::LbfgsArgs a{};
-    a.n = n; a.B = B; a.ld = ld;
-    a.x = x; a.g = g; a.xp = xp; a.gp = gp; a.d = d; a.lm_s = lm_s; a.lm_y = lm_y; a.lm_ys = lm_ys; a.lm_alpha = lm_alpha;
-    a.pf = pf; a.ds = ds; a.feval = feval; a.is = is;
-    a.p = to_kernel_params(p);
-    a.vs = wave ? 1 : ld; a.ps = wave ? n : 1;
-    return a;
-  }
-  // a fresh run: every IS_* / DS_* row zero
-  hipError_t reset(hipStream_t st) const {
-    const hipError_t e = hipMemsetAsync(is, 0, sizeof(int) * anet::IS_COUNT_ * ld, st);
-    return e != hipSuccess ? e : hipMemsetAsync(ds, 0, sizeof(double) * anet::DS_COUNT_ * ld, st);
-  }
-};
+using anet::LbfgsLayout;  // (workspace.h)
 
+// The kernels' view of a layout for B problems.  wave: the internal vectors (xp, gp, d, lm_s, lm_y) problem-major (element i
+// of problem b at [i + b*n]: one wave per problem), else batch-minor (one lane per problem).  What a call site has beyond
+// this -- variable map, step bound, cancel word, host callbacks -- it sets by field name.
+static anet::LbfgsArgs lbfgs_args(const LbfgsLayout &L, int64_t B, const anet_lbfgs_params &p, bool wave) {
+  anet::LbfgsArgs a{};
+  a.n = L.n; a.B = B; a.ld = L.ld;
+  a.x = L.x; a.g = L.g; a.xp = L.xp; a.gp = L.gp; a.d = L.d; a.lm_s = L.lm_s; a.lm_y = L.lm_y; a.lm_ys = L.lm_ys;
+  a.lm_alpha = L.lm_alpha; a.pf = L.pf; a.ds = L.ds; a.feval = L.feval; a.is = L.is;
+  a.p = to_kernel_params(p);
+  a.vs = wave ? 1 : L.ld; a.ps = wave ? L.n : 1;
+  return a;
+}
+// a fresh run: every IS_* / DS_* row zero
+static hipError_t lbfgs_reset(const LbfgsLayout &L, hipStream_t st) {
+  const hipError_t e = hipMemsetAsync(L.is, 0, sizeof(int) * anet::IS_COUNT_ * L.ld, st);
+  return e != hipSuccess ? e : hipMemsetAsync(L.ds, 0, sizeof(double) * anet::DS_COUNT_ * L.ld, st);
+}
 
 // eval(): enqueue the objective at L.x -> L.feval, L.g (for all problems).  The loop advances every
 // problem by one evaluation per pass and polls an "any problem still running" flag every `poll` passes.
@@ -60,12 +45,12 @@ static int lbfgs_drive(anet_ctx *ctx, LbfgsLayout &L, int64_t B, const anet_lbfg
                        int sb_on = 0, double sb_xmin = 0.0, const int32_t *cancel = nullptr) {
   int rc = ensure_counter(ctx);
   if (rc) return rc;
-  if (reset) ANET_HIP(ctx, L.reset(st));  // (a caller that pre-marks problems as finished resets the state itself)
+  if (reset) ANET_HIP(ctx, lbfgs_reset(L, st));  // (a caller that pre-marks problems as finished resets the state itself)
   // one wave per problem (DPP reductions, internal vectors problem-major) whenever the problem fits a wave's registers, at every
   // batch size -- at 131072 x 29 variables the lane-per-problem update kernel took 1.67 ms per tick (three times the objective
   // evaluation), the wave kernel 0.4 ms --; otherwise one lane per problem (internal vectors batch-minor)
   const bool wave = L.n <= 128 && prm.mem_size <= 64;
-  anet::LbfgsArgs a = L.args(B, prm, wave);
+  anet::LbfgsArgs a = lbfgs_args(L, B, prm, wave);
   a.map_T = map_T; a.map_nw = map_nw;
   a.sb_on = sb_on; a.sb_lo = map_nw; a.sb_xmin = sb_xmin;
   a.cancel = (const int *)cancel;
@@ -129,9 +114,9 @@ static void launch_mvie_one_launch(const anet::LbfgsArgs &la, const anet::MvieAr
 
 // (shift 4: evaluation counts of an L-BFGS run, up to 65535; shift 0: Newton-step counts of the interior point, up to 4095)
 __device__ __forceinline__ int order_bucket(int v, int shift) {
-  const int top = (kOrderBuckets << shift) - 1;
+  const int top = (anet::kOrderBuckets << shift) - 1;
   v = v < 0 ? 0 : (v > top ? top : v);
-  return kOrderBuckets - 1 - (v >> shift);  // descending
+  return anet::kOrderBuckets - 1 - (v >> shift);  // descending
 }
 __global__ void k_order_hist(const int *counts, int64_t B, int *hist, int shift) {
   const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -193,7 +178,7 @@ int launch_order_impl(anet_ctx *ctx, int64_t batch, const int32_t *counts, int32
   if (!counts || !launch_order || !work) return fail(ctx, ANET_ERR_INVALID, "anet_launch_order_from_counts_dev: NULL pointer");
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)((batch + 255) / 256)), block(256);
-  ANET_HIP(ctx, hipMemsetAsync(work, 0, sizeof(int) * kOrderBuckets, st));
+  ANET_HIP(ctx, hipMemsetAsync(work, 0, sizeof(int) * anet::kOrderBuckets, st));
   hipLaunchKernelGGL(k_order_hist, grid, block, 0, st, counts, batch, work, shift);
   hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(1024), 0, st, work);
   hipLaunchKernelGGL(k_order_scatter, grid, block, 0, st, counts, batch, work, launch_order, shift);
@@ -257,15 +242,18 @@ const char *anet_lbfgs_strerror(int code) {
   }
 }
 
-// status / iters / evals rows of d_res (k_lbfgs_results: ld int32 each) and the cost -> the caller's host arrays
-static int download_results(anet_ctx *ctx, int64_t batch, int64_t ld, const int *d_res, const double *d_cost, int32_t *status,
+// the status / iters / evals rows k_lbfgs_results filled and the cost -> the caller's host arrays
+static int download_results(anet_ctx *ctx, int64_t batch, const anet::LbfgsResultRows &r, const double *d_cost, int32_t *status,
                             int32_t *iters, int32_t *evals, double *cost, hipStream_t s0) {
-  if (status) ANET_HIP(ctx, hipMemcpyAsync(status, d_res, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
-  if (iters) ANET_HIP(ctx, hipMemcpyAsync(iters, d_res + ld, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
-  if (evals) ANET_HIP(ctx, hipMemcpyAsync(evals, d_res + 2 * ld, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
+  if (status) ANET_HIP(ctx, hipMemcpyAsync(status, r.status, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
+  if (iters) ANET_HIP(ctx, hipMemcpyAsync(iters, r.iters, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
+  if (evals) ANET_HIP(ctx, hipMemcpyAsync(evals, r.evals, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
   if (cost) ANET_HIP(ctx, hipMemcpyAsync(cost, d_cost, sizeof(double) * batch, hipMemcpyDeviceToHost, s0));
   return ANET_OK;
 }
+
+// the result rows in a Stager's units: rows of ld doubles
+static int64_t result_row_fields(int64_t ld) { return (anet::lbfgs_result_rows(nullptr, ld).doubles + ld - 1) / ld; }
 
 static int check_lbfgs(anet_ctx *ctx, int n, const anet_lbfgs_params *params, int max_evals) {
   const int code = anet_lbfgs_check_params(n, params);
@@ -285,24 +273,24 @@ int anet_lbfgs_mvie(anet_ctx *ctx, int64_t batch, int M, const double *A, double
   if (!A || !x) return fail(ctx, ANET_ERR_INVALID, "anet_lbfgs_mvie: NULL pointer");
   const int n = 9, m = params->mem_size, npf = params->past > 1 ? params->past : 1;
   Stager st;
-  const int64_t wdoubles = LbfgsLayout::doubles(n, m, npf, 1);
+  const int64_t wdoubles = anet::lbfgs_layout(nullptr, n, m, npf, 1).doubles;
   const int64_t mx = 3 * (int64_t)M > n ? 3 * (int64_t)M : n;
-  rc = make_stager(ctx, batch, mx, 3 * (int64_t)M + n + wdoubles + 3, &st);
+  const int64_t rfields = result_row_fields(batch == 1 ? 1 : anet_recommended_ld(batch));  // (the stager's row stride)
+  rc = make_stager(ctx, batch, mx, 3 * (int64_t)M + n + wdoubles + rfields, &st);
   if (rc) return rc;
   double *d_A, *d_x0;
   if ((rc = st.upload(A, 3 * (int64_t)M, &d_A))) return rc;
   if ((rc = st.upload(x, n, &d_x0))) return rc;
-  LbfgsLayout L{n, m, npf, st.ld};
-  L.carve(st.reserve(wdoubles));
-  int *d_res = (int *)st.reserve(3);  // status, iters, evals rows (int32, ld each; 3*ld doubles is ample)
+  LbfgsLayout L = anet::lbfgs_layout(st.reserve(wdoubles), n, m, npf, st.ld);
+  const anet::LbfgsResultRows R = anet::lbfgs_result_rows(st.reserve(rfields), st.ld);
   hipStream_t s0 = ctx->stream;
   ANET_HIP(ctx, hipMemcpyAsync(L.x, d_x0, sizeof(double) * n * st.ld, hipMemcpyDeviceToDevice, s0));
   anet::MvieArgs ma{d_A, L.x, L.feval, L.g, L.is, batch, st.ld, M, smooth_eps, penalty_wt};
   const dim3 grid((unsigned)((batch + 63) / 64)), block(64);
   if (params->mem_size <= 64) {
     // one wave per problem, the whole optimisation in one launch (k_lbfgs_mvie_persistent)
-    ANET_HIP(ctx, L.reset(s0));
-    launch_mvie_one_launch(L.args(batch, *params, true), ma, max_evals, s0);
+    ANET_HIP(ctx, lbfgs_reset(L, s0));
+    launch_mvie_one_launch(lbfgs_args(L, batch, *params, true), ma, max_evals, s0);
     ANET_HIP(ctx, hipGetLastError());
   } else {
     rc = lbfgs_drive(ctx, L, batch, *params, max_evals, s0, [&]() -> int {
@@ -313,15 +301,15 @@ int anet_lbfgs_mvie(anet_ctx *ctx, int64_t batch, int M, const double *A, double
     if (rc) return rc;
   }
   hipLaunchKernelGGL(k_lbfgs_results, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s0, L.is, L.ds, batch,
-                     st.ld, d_res, d_res + st.ld, d_res + 2 * st.ld, L.feval);
+                     st.ld, R.status, R.iters, R.evals, L.feval);
   ANET_HIP(ctx, hipGetLastError());
-  if ((rc = download_results(ctx, batch, st.ld, d_res, L.feval, status, iters, evals, f, s0))) return rc;
+  if ((rc = download_results(ctx, batch, R, L.feval, status, iters, evals, f, s0))) return rc;
   return st.download(L.x, n, x);
 }
 
 int64_t anet_lbfgs_workspace(int n, int64_t ld, const anet_lbfgs_params *params) {
   if (!params || n < 1 || ld < 1) return 0;
-  return LbfgsLayout::doubles(n, params->mem_size, params->past > 1 ? params->past : 1, ld);
+  return anet::lbfgs_layout(nullptr, n, params->mem_size, params->past > 1 ? params->past : 1, ld).doubles;
 }
 
 int anet_lbfgs_optimize_dev(anet_ctx *ctx, int n, int64_t batch, int64_t ld, double *x, double *f, double *g,
@@ -335,8 +323,7 @@ int anet_lbfgs_optimize_dev(anet_ctx *ctx, int n, int64_t batch, int64_t ld, dou
   if (batch == 0) return ANET_OK;
   if (!x || !f || !g || !proc_evaluate || !work) return fail(ctx, ANET_ERR_INVALID, "anet_lbfgs_optimize_dev: NULL pointer");
   const int m = params->mem_size, npf = params->past > 1 ? params->past : 1;
-  LbfgsLayout L{n, m, npf, ld};
-  L.carve(work);
+  LbfgsLayout L = anet::lbfgs_layout(work, n, m, npf, ld);
   L.x = x;      // the caller's buffers: what its callback reads and fills
   L.g = g;
   L.feval = f;
@@ -374,28 +361,28 @@ int anet_lbfgs_optimize_host(anet_ctx *ctx, int n, double *x, double *f, anet_lb
   // call, not the context's scratch: the callbacks run while the state is live and may call any host-staged entry point on
   // the same context (anet_minco_cost_grad, anet_traj_*, another anet_lbfgs_optimize_host ...), which re-carve -- or free and
   // re-allocate -- that scratch (lbfgs::lbfgs_optimize<V>, Piece and Trajectory all use Context::thread_default()).
-  const int64_t wd = LbfgsLayout::doubles(n, m, npf, 1);
+  LbfgsLayout L{};
+  int *d_cancel = nullptr;
+  auto layout = [&](void *w) { anet::Cursor c(w); L = anet::lbfgs_layout(c, n, m, npf, 1); d_cancel = c.take<int>(1); return c.bytes; };
   struct OwnBuffer {
     void *p = nullptr;
     ~OwnBuffer() { if (p) (void)hipFree(p); }
   } own;
   {
-    hipError_t e = hipMalloc(&own.p, sizeof(double) * (size_t)(wd + 4));
+    hipError_t e = hipMalloc(&own.p, (size_t)layout(nullptr));
     if (e != hipSuccess) {
       own.p = nullptr;
       return fail(ctx, ANET_ERR_NOMEM, std::string("anet_lbfgs_optimize_host: hipMalloc: ") + hipGetErrorString(e));
     }
   }
   int rc = ANET_OK;
-  LbfgsLayout L{n, m, npf, 1};
-  L.carve((double *)own.p);
-  int *d_cancel = (int *)((double *)own.p + wd + 2);
+  (void)layout(own.p);
   hipStream_t st = ctx->stream;
   std::vector<double> hg((size_t)n), hxp((size_t)n), hd((size_t)n);
-  ANET_HIP(ctx, L.reset(st));
+  ANET_HIP(ctx, lbfgs_reset(L, st));
   ANET_HIP(ctx, hipMemsetAsync(d_cancel, 0, sizeof(int), st));
   ANET_HIP(ctx, hipMemcpyAsync(L.x, x, sizeof(double) * n, hipMemcpyHostToDevice, st));
-  anet::LbfgsArgs a = L.args(1, *params, false);
+  anet::LbfgsArgs a = lbfgs_args(L, 1, *params, false);
   a.cancel = d_cancel;
   a.host_pg = proc_progress ? 1 : 0;
   a.host_sb = proc_stepbound ? 1 : 0;
@@ -446,18 +433,17 @@ int anet_lbfgs_optimize_host(anet_ctx *ctx, int n, double *x, double *f, anet_lb
   return ANET_OK;
 }
 
+// Does the workspace of N pieces end in the tail the two launches hand the parked optimisers over in?  Where the two-launch form
+// of the one-launch shape can run: enough variables.  Whether a BATCH takes it is the context's decision -- lbfgs_minco_dev_impl,
+// by the device's compute units -- and does not enter the size: the workspace is enough for either form at any batch <= ld.
+static bool minco_ws_has_tail(int N) {
+  return anet::tuning().lbfgs_split_evals > 1 && 3 * (N - 1) + N >= anet::tuning().lbfgs_split_min_vars;
+}
+
 int64_t anet_lbfgs_minco_workspace(int s, int n_pieces, int64_t ld, const anet_lbfgs_params *params) {
   if (!params || params->mem_size <= 0) return -1;
-  const int n = 3 * (n_pieces - 1) + n_pieces;
-  const int npf = params->past > 1 ? params->past : 1;
-  // L-BFGS state + cost/grad workspace + gradP + gradT ...
-  int64_t w = LbfgsLayout::doubles(n, params->mem_size, npf, ld) + anet_minco_cost_grad_workspace(s, n_pieces, ld) + (int64_t)n * ld;
-  // ... then, where the two-launch form of the one-launch shape can run (enough variables; whether a BATCH takes it is the
-  // context's decision -- lbfgs_minco_dev_impl, by the device's compute units -- and does not enter the size: a workspace of
-  // this size is enough for either form at any batch <= ld), the tail the two launches hand the parked optimisers over in
-  if (anet::tuning().lbfgs_split_evals > 1 && n >= anet::tuning().lbfgs_split_min_vars)
-    w += ResumeTail::doubles(anet::kPersistContDoubles, ld);
-  return w;
+  const int n = 3 * (n_pieces - 1) + n_pieces, npf = params->past > 1 ? params->past : 1;
+  return anet::lbfgs_minco_ws(nullptr, s, n_pieces, ld, params->mem_size, npf, n, minco_ws_has_tail(n_pieces)).doubles;
 }
 
 // Order of the second launch of a two-launch L-BFGS run (lbfgs_minco_persistent.h PersistArgs::park): larger = expected to need more
@@ -546,11 +532,8 @@ static int lbfgs_minco_dev_impl(anet_ctx *ctx, int s, int c, int n_pieces, int64
   if (!head || !tail || !T || (N > 1 && !wps) || !work || ld < batch)
     return fail(ctx, ANET_ERR_INVALID, "anet_lbfgs_minco_dev: NULL pointer or ld < batch");
   const int m = params->mem_size, npf = params->past > 1 ? params->past : 1;
-  LbfgsLayout L{n, m, npf, ld};
-  L.carve(work);
-  double *w_cg = work + LbfgsLayout::doubles(n, m, npf, ld);
-  double *w_gP = w_cg + anet_minco_cost_grad_workspace(s, N, ld);
-  double *w_gT = w_gP + (int64_t)3 * (N - 1) * ld;
+  const anet::LbfgsMincoWs W = anet::lbfgs_minco_ws(work, s, N, ld, m, npf, n, minco_ws_has_tail(N));
+  LbfgsLayout L = W.opt;
   hipStream_t st = (hipStream_t)stream;
   const dim3 g256((unsigned)((batch + 255) / 256)), b256(256);
   anet::MapArgs mp{L.x, wps, T, batch, ld, nw, nt, 0};
@@ -561,7 +544,7 @@ static int lbfgs_minco_dev_impl(anet_ctx *ctx, int s, int c, int n_pieces, int64
   // their gradient goes straight into g, the update kernel writes T = forward_T(tau) next to x, and the
   // propagate kernel applies dT/dtau to the duration gradient.
   const double *wps_eval = nw ? L.x : wps;
-  double *gP_out = nw ? L.g : w_gP, *gT_out = nt ? L.g + (int64_t)nw * ld : w_gT;
+  double *gP_out = nw ? L.g : W.gP, *gT_out = nt ? L.g + (int64_t)nw * ld : W.gT;
   const double *tau = nt ? L.x + (int64_t)nw * ld : nullptr;
   // One launch, one wave per problem (lbfgs_minco_persistent.h) whenever the problem fits a wave: every problem runs
   // until ITS OWN stop instead of the batch advancing in lockstep, four launches per evaluation.  The launch-per-
@@ -622,8 +605,7 @@ static int lbfgs_minco_dev_impl(anet_ctx *ctx, int s, int c, int n_pieces, int64
     const int split_evals = t.lbfgs_split_evals;
     const bool two_launches = split_evals > 1 && batch >= t.lbfgs_split_min_batch.at(ctx->cus) && n >= t.lbfgs_split_min_vars &&
                               !launch_order && max_evals > split_evals;
-    ResumeTail rt{anet::kPersistContDoubles, ld};
-    rt.carve(w_gP + (int64_t)n * ld);
+    const anet::ResumeTail &rt = W.tail;  // (two_launches implies minco_ws_has_tail)
     auto launch = [&](auto kernel, size_t fixed_bytes) -> int {
       const size_t lds = fixed_bytes + row_bytes;
       if (!two_launches) {
@@ -679,7 +661,7 @@ static int lbfgs_minco_dev_impl(anet_ctx *ctx, int s, int c, int n_pieces, int64
   // the lockstep shape: the same minimum-duration bound (one maximum over the duration variables per iteration) and the
   // same cancel word, looked at after every successful line search (lbfgs.hpp:557-565, 580-587)
   rc = lbfgs_drive(ctx, L, batch, *params, max_evals, st, [&]() -> int {
-    return cost_grad_dev_impl(ctx, s, c, N, batch, ld, head, tail, wps_eval, T, hpolys, pen, w_cg, L.feval, gP_out,
+    return cost_grad_dev_impl(ctx, s, c, N, batch, ld, head, tail, wps_eval, T, hpolys, pen, W.cg.co, L.feval, gP_out,
                               gT_out, nullptr, st, tau);
   }, nt ? T : nullptr, nw, true, step_bound, tau_min, ctx->cancel_flag);
   return rc ? rc : finish();
@@ -728,7 +710,8 @@ static int lbfgs_minco_host_impl(anet_ctx *ctx, int s, int c, int n_pieces, int6
   int64_t mx = nco > nhp ? nco : nhp;
   if (mx < 3 * (int64_t)c) mx = 3 * c;
   Stager st;
-  rc = make_stager(ctx, batch, mx, 6 * (int64_t)c + 3 * (int64_t)(N - 1) + N + nhp + nco + wdoubles + 4, &st);
+  const int64_t rfields = result_row_fields(ld_h);
+  rc = make_stager(ctx, batch, mx, 6 * (int64_t)c + 3 * (int64_t)(N - 1) + N + nhp + nco + wdoubles + 1 + rfields, &st);
   if (rc) return rc;
   double *d_head, *d_tail, *d_wps, *d_T, *d_hp = nullptr;
   if ((rc = st.upload(head, 3 * c, &d_head))) return rc;
@@ -737,13 +720,13 @@ static int lbfgs_minco_host_impl(anet_ctx *ctx, int s, int c, int n_pieces, int6
   if ((rc = st.upload(T, N, &d_T))) return rc;
   if (nhp && (rc = st.upload(hpolys, nhp, &d_hp))) return rc;
   double *d_co = st.reserve(nco), *d_work = st.reserve(wdoubles), *d_cost = st.reserve(1);
-  int *d_res = (int *)st.reserve(3);
+  const anet::LbfgsResultRows R = anet::lbfgs_result_rows(st.reserve(rfields), st.ld);
   rc = lbfgs_minco_dev_impl(ctx, s, c, N, batch, st.ld, d_head, d_tail, d_wps, d_T, d_hp, pen, params, opt_flags,
-                            max_evals, min_duration, nullptr, d_work, d_cost, coeffs_out ? d_co : nullptr, d_res, d_res + st.ld,
-                            d_res + 2 * st.ld, ctx->stream);
+                            max_evals, min_duration, nullptr, d_work, d_cost, coeffs_out ? d_co : nullptr, R.status, R.iters, R.evals,
+                            ctx->stream);
   if (rc) return rc;
   hipStream_t s0 = ctx->stream;
-  if ((rc = download_results(ctx, batch, st.ld, d_res, d_cost, status, iters, evals, cost, s0))) return rc;
+  if ((rc = download_results(ctx, batch, R, d_cost, status, iters, evals, cost, s0))) return rc;
   if (N > 1 && (rc = st.download(d_wps, (int64_t)(N - 1) * 3, wps))) return rc;
   if ((rc = st.download(d_T, N, T))) return rc;
   if (coeffs_out && (rc = st.download(d_co, nco, coeffs_out))) return rc;
@@ -791,9 +774,7 @@ static int firi_check(anet_ctx *ctx, int64_t batch, int n_bd, int max_points, in
 // doubles of device workspace of anet_firi_dev: ellipsoid state, forward points, MVIE rows, L-BFGS state, flags
 int64_t anet_firi_workspace(int64_t batch, int max_points, int max_rows) {
   if (batch < 0 || max_points < 0 || max_rows < 4) return -1;
-  const int64_t Np = max_points > 0 ? max_points : 1, ld = anet_recommended_ld(batch);
-  return batch * anet::kFiriEll + batch * Np * 4 + 3 * (int64_t)max_rows * ld + LbfgsLayout::doubles(9, 18, 3, ld) +
-         (batch * (2 + Np)) / 2 + 16;
+  return anet::firi_ws(nullptr, batch, anet_recommended_ld(batch), max_points > 0 ? max_points : 1, max_rows).doubles;
 }
 
 int anet_firi_dev(anet_ctx *ctx, int64_t batch, int n_bd, int max_points, int max_rows, const double *bd,
@@ -821,38 +802,34 @@ int anet_firi_var_dev(anet_ctx *ctx, int64_t batch, int n_bd, int max_points, in
   // firi.hpp:212-217
   anet_lbfgs_params lp;
   anet_lbfgs_default_params(&lp);
-  lp.mem_size = 18; lp.g_epsilon = 0.0; lp.min_step = 1.0e-32; lp.past = 3; lp.delta = 1.0e-7;
-  const int n = 9, m = lp.mem_size, npf = lp.past;
+  lp.mem_size = anet::kFiriLbfgsMem; lp.g_epsilon = 0.0; lp.min_step = 1.0e-32; lp.past = anet::kFiriLbfgsPast; lp.delta = 1.0e-7;
   const int64_t ld = anet_recommended_ld(batch);
-  const int64_t w_l = LbfgsLayout::doubles(n, m, npf, ld);
-  const size_t n_ell = (size_t)batch * anet::kFiriEll, n_fpc = (size_t)batch * Np * 4, n_hp = (size_t)batch * H * 4;
-  const size_t n_A = (size_t)3 * H * ld;
-  double *d_ell = work, *d_fpc = d_ell + n_ell, *d_A = d_fpc + n_fpc, *d_l = d_A + n_A;
-  int *d_flag = (int *)(d_l + w_l), *d_mok = d_flag + (size_t)batch * Np, *d_np0 = d_mok + batch;
+  const size_t n_hp = (size_t)batch * H * 4;
+  const anet::FiriWs W = anet::firi_ws(work, batch, ld, Np, H);
+  const LbfgsLayout &L = W.opt;
+  double *d_ell = W.ell, *d_A = W.A;
   hipStream_t st = (hipStream_t)stream;
   const int *d_np = n_points;
   if (max_points == 0) {  // no obstacle points at all: a zero count per corridor
-    ANET_HIP(ctx, hipMemsetAsync(d_np0, 0, sizeof(int) * batch, st));
-    d_np = d_np0;
+    ANET_HIP(ctx, hipMemsetAsync(W.np0, 0, sizeof(int) * batch, st));
+    d_np = W.np0;
   }
   ANET_HIP(ctx, hipMemsetAsync(hpoly, 0, sizeof(double) * n_hp, st));
-  anet::FiriArgs fa{bd, pc, d_np, a, b, d_ell, d_fpc, d_flag, hpoly, n_rows, ok, batch, n_bd, Np, H, P.epsilon};
+  anet::FiriArgs fa{bd, pc, d_np, a, b, d_ell, W.fpc, W.flag, hpoly, n_rows, ok, batch, n_bd, Np, H, P.epsilon};
   const dim3 g64((unsigned)((batch + 63) / 64)), b64(64), gB((unsigned)batch), b256(256);
   hipLaunchKernelGGL(anet::k_firi_init, g64, b64, 0, st, fa);
   ANET_HIP(ctx, hipGetLastError());
-  LbfgsLayout L{n, m, npf, ld};
-  L.carve(d_l);
   anet::FiriMvieArgs ma{hpoly, n_rows, ok, d_ell, d_A, L.x, L.is + (int64_t)anet::IS_DONE * ld, L.is + (int64_t)anet::IS_RET * ld,
-                        d_mok, batch, ld, H};
+                        W.mok, batch, ld, H};
   anet::MvieArgs ev{d_A, L.x, L.feval, L.g, L.is, batch, ld, H, P.smooth_eps, P.penalty_wt};
-  const anet::LbfgsArgs la = L.args(batch, lp, true);  // (one wave per corridor; no "still running" counter)
+  const anet::LbfgsArgs la = lbfgs_args(L, batch, lp, true);  // (one wave per corridor; no "still running" counter)
   fa.iters = iterations; ma.iters = iterations;
   for (int loop = 0; loop < P.iterations; ++loop) {
     fa.pass = loop; ma.pass = loop;
     hipLaunchKernelGGL(anet::k_firi_planes, gB, b256, 0, st, fa);
     ANET_HIP(ctx, hipGetLastError());
     if (loop == P.iterations - 1) break;
-    ANET_HIP(ctx, L.reset(st));
+    ANET_HIP(ctx, lbfgs_reset(L, st));
     hipLaunchKernelGGL(anet::k_firi_mvie_setup, gB, b256, sizeof(double) * H * 4, st, ma);
     ANET_HIP(ctx, hipGetLastError());
     launch_mvie_one_launch(la, ev, P.mvie_max_evals, st);  // the whole MVIE optimisation in one launch, one wave per corridor
@@ -888,12 +865,18 @@ int anet_firi_var(anet_ctx *ctx, int64_t batch, int n_bd, int max_points, int ma
   const int H = max_rows, Np = max_points > 0 ? max_points : 1;
   const size_t n_bdv = (size_t)batch * n_bd * 4, n_pc = (size_t)batch * Np * 3, n_ab = (size_t)batch * 3;
   const size_t n_hp = (size_t)batch * H * 4, n_ell = (size_t)batch * 15;
-  const size_t n_work = (size_t)anet_firi_workspace(batch, max_points, max_rows);
-  rc = ensure_scratch(ctx, sizeof(double) * (n_bdv + n_pc + 2 * n_ab + n_hp + n_ell + n_work + (size_t)(4 * batch) / 2 + 16));
+  const int64_t n_work = anet_firi_workspace(batch, max_points, max_rows);
+  double *d_bd, *d_pc, *d_a, *d_b, *d_hp, *d_el, *d_work;
+  int *d_np, *d_nh, *d_ok, *d_it;
+  rc = stage_scratch(ctx, [&](void *w) {
+    anet::Cursor c(w);
+    d_bd = c.take<double>(n_bdv); d_pc = c.take<double>(n_pc); d_a = c.take<double>(n_ab); d_b = c.take<double>(n_ab);
+    d_hp = c.take<double>(n_hp); d_el = c.take<double>(n_ell); d_work = c.take<double>(n_work);
+    d_np = c.take<int>(batch); d_nh = c.take<int>(batch); d_ok = c.take<int>(batch); d_it = c.take<int>(batch);
+    (void)c.spare(16);
+    return c.bytes;
+  });
   if (rc) return rc;
-  double *d_bd = (double *)ctx->scratch, *d_pc = d_bd + n_bdv, *d_a = d_pc + n_pc, *d_b = d_a + n_ab, *d_hp = d_b + n_ab;
-  double *d_el = d_hp + n_hp, *d_work = d_el + n_ell;
-  int *d_np = (int *)(d_work + n_work), *d_nh = d_np + batch, *d_ok = d_nh + batch, *d_it = d_ok + batch;
   hipStream_t st = ctx->stream;
   if (iterations) {  // (host array: checked here; the device variant clamps instead, it cannot look without a synchronisation)
     for (int64_t b = 0; b < batch; ++b)
@@ -946,9 +929,13 @@ int anet_polytope_depth(anet_ctx *ctx, int64_t batch, int max_rows, const double
   if (batch == 0) return ANET_OK;
   if (!hpoly || !depth) return fail(ctx, ANET_ERR_INVALID, "anet_polytope_depth: NULL pointer");
   const size_t n_hp = (size_t)batch * max_rows * 4;
-  int rc = ensure_scratch(ctx, sizeof(double) * (n_hp + 4 * (size_t)batch));
+  double *d_hp, *d_depth, *d_pt;
+  int rc = stage_scratch(ctx, [&](void *w) {
+    anet::Cursor c(w);
+    d_hp = c.take<double>(n_hp); d_depth = c.take<double>(batch); d_pt = c.take<double>(3 * batch);
+    return c.bytes;
+  });
   if (rc) return rc;
-  double *d_hp = (double *)ctx->scratch, *d_depth = d_hp + n_hp, *d_pt = d_depth + batch;
   hipStream_t st = ctx->stream;
   ANET_HIP(ctx, hipMemcpyAsync(d_hp, hpoly, sizeof(double) * n_hp, hipMemcpyHostToDevice, st));
   rc = anet_polytope_depth_dev(ctx, batch, max_rows, d_hp, normalise, d_depth, point ? d_pt : nullptr, st);

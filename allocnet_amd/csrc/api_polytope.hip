@@ -67,11 +67,16 @@ int anet_polytope_vertices(anet_ctx *ctx, int64_t batch, int max_rows, const dou
   if (batch == 0) return ANET_OK;
   if (!hpoly || !verts || !count) return fail(ctx, ANET_ERR_INVALID, "anet_polytope_vertices: NULL pointer");
   const size_t n_hp = (size_t)batch * max_rows * 4, n_v = (size_t)batch * max_vertices * 3, n_a = (size_t)batch * max_vertices * 2;
-  // doubles: depth | hpoly | verts | active (uint64) | count, status (int32, two per double)
-  if ((rc = ensure_scratch(ctx, sizeof(double) * ((size_t)batch + n_hp + n_v + n_a + (size_t)batch + 2)))) return rc;
-  double *d_depth = (double *)ctx->scratch, *d_hp = d_depth + batch, *d_v = d_hp + n_hp;
-  uint64_t *d_act = (uint64_t *)(d_v + n_v);
-  int32_t *d_cnt = (int32_t *)(d_act + n_a), *d_st = d_cnt + batch;
+  double *d_depth, *d_hp, *d_v;
+  uint64_t *d_act;
+  int32_t *d_cnt, *d_st;
+  rc = stage_scratch(ctx, [&](void *w) {  // (the depths lead: anet_polytope_vertices_dev keeps them there; active directly behind verts)
+    anet::Cursor c(w);
+    d_depth = c.take<double>(batch); d_hp = c.take<double>(n_hp); d_v = c.take<double>(n_v); d_act = c.take<uint64_t>(n_a);
+    d_cnt = c.take<int32_t>(batch); d_st = c.take<int32_t>(batch); (void)c.spare(2);
+    return c.bytes;
+  });
+  if (rc) return rc;
   hipStream_t st = ctx->stream;
   ANET_HIP(ctx, hipMemcpyAsync(d_hp, hpoly, sizeof(double) * n_hp, hipMemcpyHostToDevice, st));
   // (slots behind count[b] are not written by the kernel: the caller reads zeros there)

@@ -73,14 +73,18 @@ int anet_qp_assemble(anet_ctx *ctx, int s, int n_pieces, int64_t batch, int res,
   anet_qp_dims dm;
   if (anet_qp_dims_of(s, n_pieces, res, rows, &dm)) return fail(ctx, ANET_ERR_INVALID, "anet_qp_assemble: bad row counts");
   const size_t n_state = 18 * (size_t)batch, n_T = (size_t)n_pieces * batch, n_hp = (size_t)batch * n_pieces * M * 4;
-  const size_t n_rows = ((size_t)n_pieces * batch + 1) / 2;  // int32 pairs in doubles
   const size_t nQ = (size_t)(dm.n * dm.n) * batch, nA = (size_t)(dm.m_e * dm.n) * batch, nb = (size_t)dm.m_e * batch;
   const size_t nG = (size_t)(dm.m_g * dm.n) * batch, nh = (size_t)dm.m_g * batch;
-  int rc = ensure_scratch(ctx, sizeof(double) * (n_state + n_T + n_hp + n_rows + nQ + nA + nb + nG + nh + 8));
+  double *d_state, *d_T, *d_hp, *d_Q, *d_A, *d_b, *d_G, *d_h;
+  int32_t *d_rows;
+  int rc = stage_scratch(ctx, [&](void *w) {
+    anet::Cursor c(w);
+    d_state = c.take<double>(n_state); d_T = c.take<double>(n_T); d_hp = c.take<double>(n_hp); d_rows = c.take<int32_t>(n_T);
+    d_Q = c.take<double>(nQ); d_A = c.take<double>(nA); d_b = c.take<double>(nb); d_G = c.take<double>(nG); d_h = c.take<double>(nh);
+    (void)c.spare(8);
+    return c.bytes;
+  });
   if (rc) return rc;
-  double *d_state = (double *)ctx->scratch, *d_T = d_state + n_state, *d_hp = d_T + n_T;
-  int32_t *d_rows = (int32_t *)(d_hp + n_hp);
-  double *d_Q = d_hp + n_hp + n_rows, *d_A = d_Q + nQ, *d_b = d_A + nA, *d_G = d_b + nb, *d_h = d_G + nG;
   hipStream_t st = ctx->stream;
   ANET_HIP(ctx, hipMemcpyAsync(d_state, state, sizeof(double) * n_state, hipMemcpyHostToDevice, st));
   ANET_HIP(ctx, hipMemcpyAsync(d_T, T, sizeof(double) * n_T, hipMemcpyHostToDevice, st));
@@ -107,14 +111,8 @@ void anet_qp_default_settings(anet_qp_settings *s) {
   s->method = ANET_QP_METHOD_INTERIOR_POINT;
 }
 
-// the parked state of one interior-point problem (qp_ipm.h IpmArgs::cont): the iterate's ny doubles, then its scalars
-static int64_t qp_cont_doubles(int s, int n_pieces) { return (int64_t)3 * s * (n_pieces + 1) + anet::kIpmContScalars; }
-
 int64_t anet_qp_solve_workspace(int s, int n_pieces, int64_t batch, int res, int M) {
-  const int64_t m = 3 * (6 + (int64_t)s * (n_pieces - 1)) + (int64_t)n_pieces * res * (M + 12);
-  // z, y, residuals; then (interior point, two-launch form) the tail the two launches hand the parked problems over in, and six
-  // doubles of slack
-  return 2 * m * batch + 2 * batch + ResumeTail::doubles(qp_cont_doubles(s, n_pieces), batch) + 6;
+  return anet::qp_solve_ws(nullptr, s, n_pieces, batch, res, M).doubles;
 }
 
 // Second part of a two-launch interior-point solve: what order its workgroups take the problems in.  Score of a parked problem,
@@ -225,11 +223,11 @@ static int qp_solve_dev_impl(anet_ctx *ctx, int s, int n_pieces, int64_t batch, 
     return fail(ctx, ANET_ERR_INVALID, "anet_qp_solve: bad settings");
   if (st_.method != ANET_QP_METHOD_ADMM && st_.method != ANET_QP_METHOD_INTERIOR_POINT)
     return fail(ctx, ANET_ERR_INVALID, "anet_qp_solve: unknown method");
+  const anet::QpSolveWs W = anet::qp_solve_ws(work, s, n_pieces, batch, res, M);
   if (st_.method == ANET_QP_METHOD_INTERIOR_POINT) {
     const size_t ldsb = qp_ipm_lds(s, n_pieces, res, M);
     if (ldsb > 160 * 1024)
       return fail(ctx, ANET_ERR_UNSUPPORTED, "anet_qp_solve: problem too large for the 160 KB LDS (interior-point method)");
-    const int64_t mi = (int64_t)n_pieces * res * (M + 12);
     double tol = st_.eps_rel < st_.eps_abs ? st_.eps_rel : st_.eps_abs;
     if (!(tol > 0.0) || tol > 1e-6) tol = 1e-6;   // Newton's method: the last digits cost one or two steps
     if (tol < 1e-10) tol = 1e-10;                 // (below that the slacks of the touched rows underflow the factorisation)
@@ -237,8 +235,8 @@ static int qp_solve_dev_impl(anet_ctx *ctx, int s, int n_pieces, int64_t batch, 
     // of that order, so it asks for three more digits (one or two Newton steps)
     const double tol_plain = tol;
     if (grad_z && tol > 1e-9) tol = 1e-9;
-    anet::IpmArgs ia{state, T, hpolys, work, work + mi * batch, coeffs, obj, status, iters,
-                     residuals ? residuals : work + 2 * mi * batch, grad_T, grad_z, vjp_T, batch, n_pieces, res, M, max_vel,
+    anet::IpmArgs ia{state, T, hpolys, W.ipm().z, W.ipm().y, coeffs, obj, status, iters,
+                     residuals ? residuals : W.ipm().residuals, grad_T, grad_z, vjp_T, batch, n_pieces, res, M, max_vel,
                      max_acc, m34, tol, qp_ipm_max_iter(st_), tol_plain > tol ? tol_plain : 0.0, 0.1 * tol, 0, launch_order, 0, 0, nullptr, nullptr};
     const anet::Tuning &t = anet::tuning();
     ia.twist_min_pieces = t.ipm_twist_min_pieces;
@@ -308,9 +306,7 @@ static int qp_solve_dev_impl(anet_ctx *ctx, int s, int n_pieces, int64_t batch, 
     int rc_l;
     if (form & ANET_QP_IPM_FORM_TWO_LAUNCHES) {
       const int ny = 3 * s * (n_pieces + 1);
-      const int64_t m_adm = 3 * (6 + (int64_t)s * (n_pieces - 1)) + mi;
-      ResumeTail rt{qp_cont_doubles(s, n_pieces), batch};
-      rt.carve(work + 2 * m_adm * batch + 2 * batch);
+      const anet::ResumeTail &rt = W.tail;
       ia.cont = rt.cont;
       ia.it_stop = t.ipm_split_steps;
       rc_l = launch_throughput();
@@ -348,11 +344,10 @@ static int qp_solve_dev_impl(anet_ctx *ctx, int s, int n_pieces, int64_t batch, 
   }
   if (lds > 160 * 1024)
     return fail(ctx, ANET_ERR_UNSUPPORTED, "anet_qp_solve: the block factor of this many pieces does not fit the 160 KB LDS");
-  const int64_t m = 3 * (6 + (int64_t)s * (n_pieces - 1)) + (int64_t)n_pieces * res * (M + 12);
   int adapt = st_.adaptive_rho_interval;
   if (adapt > 0) adapt = (adapt + st_.check_termination - 1) / st_.check_termination * st_.check_termination;
-  anet::AdmmArgs a{state, T, hpolys, work, work + m * batch, coeffs, obj, status, iters,
-                   residuals ? residuals : work + 2 * m * batch, batch, n_pieces, res, M, max_vel, max_acc, m34,
+  anet::AdmmArgs a{state, T, hpolys, W.admm().z, W.admm().y, coeffs, obj, status, iters,
+                   residuals ? residuals : W.admm().residuals, batch, n_pieces, res, M, max_vel, max_acc, m34,
                    anet::AdmmParams{st_.rho, st_.sigma, st_.alpha, st_.eps_abs, st_.eps_rel, st_.max_iter,
                                     st_.check_termination, adapt, st_.scaled_termination ? 1 : 0},
                    zy_in_lds, grad_T};
@@ -416,15 +411,18 @@ static int qp_solve_host_impl(anet_ctx *ctx, int s, int n_pieces, int64_t batch,
   if (!state || !T || (M > 0 && !hpolys) || !coeffs) return fail(ctx, ANET_ERR_INVALID, "anet_qp_solve: NULL pointer");
   const size_t n = (size_t)3 * 2 * s * n_pieces;
   const size_t n_state = 18 * (size_t)batch, n_T = (size_t)n_pieces * batch, n_hp = (size_t)batch * n_pieces * M * 4;
-  const size_t n_work = (size_t)anet_qp_solve_workspace(s, n_pieces, batch, res, M);
-  const size_t n_int = (size_t)batch;  // 2 int32 arrays fit in `batch` doubles
-  int rc = ensure_scratch(ctx, sizeof(double) * (n_state + n_T + n_hp + n_work + 2 * n * batch + 3 * batch + n_int + n_T + 8));
+  const int64_t n_work = anet_qp_solve_workspace(s, n_pieces, batch, res, M);
+  double *d_state, *d_T, *d_hp, *d_work, *d_co, *d_obj, *d_res, *d_gT, *d_gz;
+  int32_t *d_status, *d_iters;
+  int rc = stage_scratch(ctx, [&](void *w) {
+    anet::Cursor c(w);
+    d_state = c.take<double>(n_state); d_T = c.take<double>(n_T); d_hp = c.take<double>(n_hp); d_work = c.take<double>(n_work);
+    d_co = c.take<double>(n * batch); d_obj = c.take<double>(batch); d_res = c.take<double>(2 * batch);
+    d_status = c.take<int32_t>(batch); d_iters = c.take<int32_t>(batch);
+    d_gT = c.take<double>(n_T); d_gz = c.take<double>(n * batch); (void)c.spare(8);
+    return c.bytes;
+  });
   if (rc) return rc;
-  double *d_state = (double *)ctx->scratch, *d_T = d_state + n_state, *d_hp = d_T + n_T, *d_work = d_hp + n_hp;
-  double *d_co = d_work + n_work, *d_obj = d_co + n * batch, *d_res = d_obj + batch;
-  int32_t *d_status = (int32_t *)(d_res + 2 * batch), *d_iters = d_status + batch;
-  double *d_gT = d_res + 2 * batch + n_int;
-  double *d_gz = d_gT + n_T;
   hipStream_t st = ctx->stream;
   ANET_HIP(ctx, hipMemcpyAsync(d_state, state, sizeof(double) * n_state, hipMemcpyHostToDevice, st));
   ANET_HIP(ctx, hipMemcpyAsync(d_T, T, sizeof(double) * n_T, hipMemcpyHostToDevice, st));

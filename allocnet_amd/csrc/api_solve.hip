@@ -287,9 +287,13 @@ int anet_piece_normalized_coeffs(anet_ctx *ctx, int s, int64_t pieces, const dou
   if (pieces == 0) return ANET_OK;
   if (!coeffs || !T || !out) return fail(ctx, ANET_ERR_INVALID, "anet_piece_normalized_coeffs: NULL pointer");
   const size_t nin = (size_t)pieces * 3 * 2 * s, nout = (size_t)pieces * 3 * (2 * s - deriv);
-  int rc = ensure_scratch(ctx, sizeof(double) * (nin + (size_t)pieces + nout));
+  double *d_co, *d_T, *d_out;
+  int rc = stage_scratch(ctx, [&](void *w) {
+    anet::Cursor c(w);
+    d_co = c.take<double>(nin); d_T = c.take<double>(pieces); d_out = c.take<double>(nout);
+    return c.bytes;
+  });
   if (rc) return rc;
-  double *d_co = (double *)ctx->scratch, *d_T = d_co + nin, *d_out = d_T + pieces;
   hipStream_t st = ctx->stream;
   ANET_HIP(ctx, hipMemcpyAsync(d_co, coeffs, sizeof(double) * nin, hipMemcpyHostToDevice, st));
   ANET_HIP(ctx, hipMemcpyAsync(d_T, T, sizeof(double) * pieces, hipMemcpyHostToDevice, st));

@@ -159,7 +159,15 @@ int anet_timenet_forward(anet_ctx *ctx, anet_timenet *net, int seq_len, int64_t 
   if (batch == 0) return ANET_OK;
   if (!state || !hpolys || !times || !count) return fail(ctx, ANET_ERR_INVALID, "anet_timenet_forward: NULL pointer");
   const size_t L = (size_t)seq_len, nb = (size_t)batch, n_state = nb * 18, n_hp = nb * anet::kTnRows * 4 * L, n_out = nb * L;
-  const size_t need = sizeof(float) * (n_state + n_hp + 3 * n_out + nb);
+  float *d_state, *d_hp, *d_times, *d_tf, *d_stop;
+  int32_t *d_count;
+  auto layout = [&](void *w) {
+    anet::Cursor c(w);
+    d_state = c.take<float>(n_state); d_hp = c.take<float>(n_hp); d_times = c.take<float>(n_out); d_tf = c.take<float>(n_out);
+    d_stop = c.take<float>(n_out); d_count = c.take<int32_t>(nb);
+    return (size_t)c.bytes;
+  };
+  const size_t need = layout(nullptr);
   if (need > net->stage_bytes) {
     if (net->stage) ANET_HIP(ctx, hipFree(net->stage));
     net->stage = nullptr;
@@ -168,9 +176,7 @@ int anet_timenet_forward(anet_ctx *ctx, anet_timenet *net, int seq_len, int64_t 
     if (e != hipSuccess) return fail(ctx, ANET_ERR_NOMEM, std::string("hipMalloc(timenet staging): ") + hipGetErrorString(e));
     net->stage_bytes = need;
   }
-  float *d_state = (float *)net->stage, *d_hp = d_state + n_state, *d_times = d_hp + n_hp, *d_tf = d_times + n_out,
-        *d_stop = d_tf + n_out;
-  int32_t *d_count = (int32_t *)(d_stop + n_out);
+  (void)layout(net->stage);
   ANET_HIP(ctx, hipMemcpyAsync(d_state, state, sizeof(float) * n_state, hipMemcpyHostToDevice, ctx->stream));
   ANET_HIP(ctx, hipMemcpyAsync(d_hp, hpolys, sizeof(float) * n_hp, hipMemcpyHostToDevice, ctx->stream));
   rc = anet_timenet_forward_dev(ctx, net, seq_len, batch, d_state, d_hp, threshold, flags, d_times, tf ? d_tf : nullptr,

@@ -16,11 +16,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "workspace_constants.h"  // kFiriEll
 
 namespace anet {
 
-// ellipsoid state per corridor: R (row-major 9), p (3), r (3), interior point of the last LP (3)
-constexpr int kFiriEll = 18;
+// ellipsoid state per corridor (kFiriEll doubles): R (row-major 9), p (3), r (3), interior point of the last LP (3)
 
 struct FiriArgs {
   const double *bd;    // [B][Mb][4]  rows h.[x;1] <= 0

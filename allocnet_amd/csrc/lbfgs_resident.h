@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "lbfgs_step.h"
+#include "workspace_constants.h"  // kPersistContLaneFields, kPersistContDoubles
 #include "wave_ops.h"
 
 namespace anet {
@@ -10,7 +11,6 @@ namespace anet {
 // A parked optimiser (PersistArgs::park / resume): kPersistContLaneFields per-lane values x 64 lanes ([field][lane]), then 64
 // wave-uniform ones.  The slots are named here, next to park / unpark, for every reader (k_lbfgs_resume_score takes PARK_U_FX,
 // PARK_U_F_HALF and PARK_U_GN2; tools/lbfgs_split_features.py reads the same layout from Python).
-constexpr int kPersistContLaneFields = 22, kPersistContDoubles = (kPersistContLaneFields + 1) * 64;
 enum { PARK_X = 0, PARK_G, PARK_D, PARK_XP, PARK_GP, PARK_PF, PARK_HS, PARK_HY = PARK_HS + 8, PARK_LANE_FIELDS_ = PARK_HY + 8 };
 enum {
   PARK_U_HYS = 0, PARK_U_FX = PARK_U_HYS + 8, PARK_U_STEP, PARK_U_FINIT, PARK_U_DGTEST, PARK_U_DSTEST, PARK_U_MU, PARK_U_NU,

@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "workspace_constants.h"  // the DS_* / IS_* state rows
 
 namespace anet {
 
@@ -23,8 +24,6 @@ struct LbfgsP {
   int max_iterations, max_linesearch;
   double min_step, max_step, f_dec_coeff, s_curv_coeff, cautious_factor, machine_prec;
 };
-enum { DS_FX = 0, DS_STEP, DS_FINIT, DS_DGTEST, DS_DSTEST, DS_MU, DS_NU, DS_SMAX, DS_COUNT_ };  // DS_SMAX: stpmax of the running line search
-enum { IS_DONE = 0, IS_RET, IS_K, IS_END, IS_BOUND, IS_COUNT, IS_BRACKT, IS_TOUCHED, IS_EVALS, IS_PHASE, IS_COUNT_ };
 enum {  // lbfgs.hpp:135-184
   LB_CONVERGENCE = 0, LB_STOP = 1, LB_CANCELED = 2,
   LBERR_INVALID_FUNCVAL = -1012, LBERR_MINIMUMSTEP = -1011, LBERR_MAXIMUMSTEP = -1010,

@@ -38,6 +38,7 @@
 #include "minco_core.h"  // fast_rcp
 #include "wave_ops.h"  // wave_sum, wave_min_f64, pair_sum
 #include "qp_admm.h"    // qblk1, fallf
+#include "workspace_constants.h"  // kIpmContScalars
 
 namespace anet {
 
@@ -117,7 +118,6 @@ struct IpmBoxRow {
 // padding each spreads them over 32.
 __host__ __device__ constexpr int ipm_ht_stride(int D) { return 3 * D + 1; }
 constexpr int kIpmRecord = 31;  // 30 sums per sample + 1 pad
-constexpr int kIpmContScalars = 16;  // scalars parked behind the node states of a stopped problem (IpmArgs::cont)
 
 template <int S>
 inline size_t qp_ipm_lds_bytes(int N, int R, int M) {

@@ -21,6 +21,8 @@ for arg in sys.argv[1:]:
     r = aa.lbfgs_minco_dev(th, tt, tw, tT, s, 3, N, B, hpolys=thp, penalty=pen, param=aa.lbfgs_parameter_t(), max_evals=40000, opt=3, ctx=ctx, return_work=True)
     torch.cuda.synchronize()
     w = r["_work"]
+    # mirrors resume_tail() at the end of lbfgs_minco_ws() (csrc/workspace.h): kPersistContDoubles per problem, two int32 rows of
+    # ld, two spare doubles, kOrderBuckets int32 bins
     tail_len = 1472 * ld + ld + 2 + 2048
     cont = w[w.numel() - tail_len: w.numel() - tail_len + 1472 * ld].reshape(ld, 23, 64)[:B].cpu().numpy()
     n = 3 * (N - 1) + N

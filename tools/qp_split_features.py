@@ -23,6 +23,7 @@ for key, s, N, B in (("snap8", 4, 8, 4096), ("jerk5", 3, 5, 4096), ("snap5", 4, 
     ny = 3 * s * (N + 1)
     m_adm = 3 * (6 + s * (N - 1)) + N * res * (M + 12)
     w = r["_work"].cpu().numpy()
+    # mirrors qp_solve_ws() (csrc/workspace.h): the front of 2 m rows, the residuals, then the tail's parked problems (ny + kIpmContScalars each)
     cont = w[2 * m_adm * B + 2 * B: 2 * m_adm * B + 2 * B + (ny + 16) * B].reshape(B, ny + 16)[:, ny:]
     out[key + "_feat"] = cont
     out[key + "_iters"] = r["iters"].cpu().numpy()
