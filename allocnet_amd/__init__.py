@@ -21,6 +21,10 @@ from .firi import (firi, firi_dev, firi_params, convex_cover, polytope_depth, fi
 from . import polytope  # noqa: F401
 from .polytope import (polytope_vertices, polytope_vertices_dev, enumerate_vs, polytope_faces, polytope_volume,  # noqa: F401
                        corridor_vertices)
+from . import sfc_opt  # noqa: F401
+from .sfc_opt import (sfc_overlap_vertices, sfc_overlap_vertices_dev, sfc_forward_p, sfc_forward_p_dev,  # noqa: F401
+                      sfc_backward_grad_p_dev, sfc_backward_p, sfc_backward_p_dev, lbfgs_minco_sfc, lbfgs_minco_sfc_dev,
+                      sfc_default_max_verts, SFC_NO_OVERLAP)
 
 from . import voxel_map  # noqa: F401
 from .voxel_map import VoxelMap, gather_boxes_dev  # noqa: F401

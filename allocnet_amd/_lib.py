@@ -92,6 +92,17 @@ PROTOTYPES = {
     "anet_polytope_depth_dev": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "anet_polytope_vertices": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_double, c_int] + [c_void_p] * 4),
     "anet_polytope_vertices_dev": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_double, c_int] + [c_void_p] * 5),
+    "anet_sfc_overlap_workspace": (c_int64, [c_int, c_int64, c_int, c_int]),
+    "anet_sfc_overlap_vertices_dev": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_double, c_int] + [c_void_p] * 5),
+    "anet_sfc_forward_p_dev": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_double] + [c_void_p] * 3),
+    "anet_sfc_backward_grad_p_dev": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int] + [c_void_p] * 8),
+    "anet_sfc_backward_p_workspace": (c_int64, [c_int, c_int, c_int64]),
+    "anet_sfc_backward_p_dev": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int] + [c_void_p] * 7),
+    "anet_sfc_workspace": (c_int64, [c_int, c_int, c_int, c_int64, c_void_p]),
+    "anet_lbfgs_minco_sfc_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_int64] + [c_void_p] * 7 + [c_int] +
+                                 [c_void_p] * 3 + [c_int, c_int, c_double, c_double] + [c_void_p] * 8),
+    "anet_lbfgs_minco_sfc": (c_int, [c_void_p, c_int, c_int, c_int, c_int64] + [c_void_p] * 7 +
+                             [c_int, c_int, c_double, c_double, c_double, c_int] + [c_void_p] * 9),
     "anet_firi_default_params": (None, [c_void_p]),
     "anet_firi": (c_int, [c_void_p, c_int64, c_int, c_int, c_int] + [c_void_p] * 10),
     "anet_firi_var": (c_int, [c_void_p, c_int64, c_int, c_int, c_int] + [c_void_p] * 11),

@@ -14,11 +14,13 @@
 //   api_flatness.hip   differential flatness: states, sampled limits, penalty gradients
 //   api_timenet.hip    the time-allocation network: weights handle, batched inference
 //   api_polytope.hip   vertex enumeration of polytopes (geo_utils::enumerateVs)
+//   api_sfc.hip        waypoints as vertex weights of corridor overlaps: the transform, its inverse, the constrained MINCO L-BFGS
 //   piece_grad_unit.hip, qp_ipm_fuse_unit.hip: kernels scheduled for ILP, reached through launch functions
 // Only what two or more units use is here.  Nothing here is exported: the library's dynamic symbols stay the anet_* entry
 // points (and the kernels).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <string.h>
 #include <string>
@@ -287,6 +289,24 @@ int resume_parked(anet_ctx *ctx, int64_t batch, const anet::ResumeTail &t, hipSt
   score(t.score);
   const int rc = launch_order_impl(ctx, batch, t.score, t.order, t.bins, st, 0);
   return rc ? rc : resume(t.order);
+}
+
+// The lockstep L-BFGS driver of api_lbfgs.hip for the other units (the update kernels are compiled there only): eval(instance)
+// enqueues one objective evaluation of the batch at L.x -> L.feval, L.g.  reset = false: the caller has zeroed the IS_* / DS_* rows
+// (lbfgs_reset_shared) and marked the problems that must not run as finished.  The other arguments are lbfgs_drive's.
+int lbfgs_drive_shared(anet_ctx *ctx, anet::LbfgsLayout &L, int64_t B, const anet_lbfgs_params &prm, int max_evals, hipStream_t st,
+                       int (*eval)(void *), void *instance, double *map_T, int map_nw, bool reset, int sb_on, double sb_xmin,
+                       const int32_t *cancel);
+int lbfgs_reset_shared(anet_ctx *ctx, const anet::LbfgsLayout &L, hipStream_t st);
+// status / iters / evals / f of a run from its state rows (row stride L.ld); any of the four may be nullptr
+int lbfgs_results_shared(anet_ctx *ctx, const anet::LbfgsLayout &L, int64_t B, int32_t *status, int32_t *iters, int32_t *evals,
+                         double *f, hipStream_t st);
+// coefficients of returned waypoints / durations: the reduced solve, then the pivoted one where the durations spread widely
+int minco_final_coeffs(anet_ctx *ctx, int s, int c, int N, int64_t batch, int64_t ld, const double *head, const double *tail,
+                       const double *wps, const double *T, double *coeffs_out, hipStream_t st);
+// the minimum-duration bound in the variable tau (gcopter's backwardT, minco_core.h backward_T); 0: none
+inline double minco_tau_min(double min_duration) {
+  return min_duration > 1.0 ? sqrt(2.0 * min_duration - 1.0) - 1.0 : (min_duration > 0.0 ? 1.0 - sqrt(2.0 / min_duration - 1.0) : 0.0);
 }
 
 // cost + gradient of a batch (api_cost_grad.hip); tau != nullptr: the durations are T = forward_T(tau) and gradT is returned as

@@ -237,6 +237,7 @@ const char *anet_lbfgs_strerror(int code) {
     case -1007: return "Relative search interval width is at least lbfgs_parameter_t::machine_prec.";
     case -1006: return "A logic error (negative line-search step) occurred.";
     case -1005: return "The current search direction increases the cost function value.";
+    case ANET_SFC_NO_OVERLAP: return "A waypoint's two polytopes have no overlap with an interior: the problem was not run.";
     case ANET_LBFGS_RUNNING: return "Still running: the evaluation budget (max_evals) was exhausted.";
     default: return "(unknown)";
   }
@@ -555,8 +556,7 @@ static int lbfgs_minco_dev_impl(anet_ctx *ctx, int s, int c, int n_pieces, int64
   const int Mrows = (pen && hpolys) ? pen->poly_rows : 0;
   // the minimum-duration bound of either shape, in the variable tau (gcopter's backwardT, minco_core.h backward_T)
   const int step_bound = (min_duration > 0.0 && nt > 0) ? 1 : 0;
-  const double tau_min = min_duration > 1.0 ? sqrt(2.0 * min_duration - 1.0) - 1.0
-                                            : (min_duration > 0.0 ? 1.0 - sqrt(2.0 / min_duration - 1.0) : 0.0);
+  const double tau_min = minco_tau_min(min_duration);
   // final parameters (x may have been reverted by a failed line search) and outputs
   auto finish = [&]() -> int {
     mp.mode = 1;
@@ -947,3 +947,29 @@ int anet_polytope_depth(anet_ctx *ctx, int64_t batch, int max_rows, const double
 }
 
 }  // extern "C"
+
+// ---- what api_sfc.hip shares with this unit (api_internal.h): the update kernels stay compiled here only ----------------------
+int lbfgs_drive_shared(anet_ctx *ctx, anet::LbfgsLayout &L, int64_t B, const anet_lbfgs_params &prm, int max_evals, hipStream_t st,
+                       int (*eval)(void *), void *instance, double *map_T, int map_nw, bool reset, int sb_on, double sb_xmin,
+                       const int32_t *cancel) {
+  return lbfgs_drive(ctx, L, B, prm, max_evals, st, [&]() -> int { return eval(instance); }, map_T, map_nw, reset, sb_on, sb_xmin,
+                     cancel);
+}
+
+int lbfgs_reset_shared(anet_ctx *ctx, const anet::LbfgsLayout &L, hipStream_t st) {
+  ANET_HIP(ctx, lbfgs_reset(L, st));
+  return ANET_OK;
+}
+
+int lbfgs_results_shared(anet_ctx *ctx, const anet::LbfgsLayout &L, int64_t B, int32_t *status, int32_t *iters, int32_t *evals,
+                         double *f, hipStream_t st) {
+  hipLaunchKernelGGL(k_lbfgs_results, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, L.is, L.ds, B, L.ld, status, iters, evals, f);
+  ANET_HIP(ctx, hipGetLastError());
+  return ANET_OK;
+}
+
+int minco_final_coeffs(anet_ctx *ctx, int s, int c, int N, int64_t batch, int64_t ld, const double *head, const double *tail,
+                       const double *wps, const double *T, double *coeffs_out, hipStream_t st) {
+  return final_coeffs(ctx, s, c, N, batch, ld, head, tail, wps, T, coeffs_out, st);
+}
+

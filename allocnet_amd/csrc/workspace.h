@@ -134,6 +134,36 @@ inline FiriWs firi_ws(double *w, int64_t batch, int64_t ld, int Np, int H) {
   return L;
 }
 
+// The corridor-constrained MINCO L-BFGS (sfc_param_kernels.h): optimiser state of (N-1) K + N variables, carved for the n_run of
+// this run | cost + gradient | waypoint rows P(xi) | dJ/dP rows | dJ/dT rows | the three norm rows per waypoint
+struct SfcWs { LbfgsLayout opt; CostGradWs cg; double *wps, *gP, *gT, *norm; int64_t doubles; };
+inline SfcWs sfc_ws(double *w, int s, int N, int K, int64_t ld, int m, int npf, int n_run) {
+  Cursor c(w);
+  SfcWs L{};
+  L.opt = lbfgs_layout(c.take<double>(lbfgs_layout(nullptr, (N - 1) * K + N, m, npf, ld).doubles), n_run, m, npf, ld);
+  L.cg = cost_grad_ws(c, s, N, ld);
+  L.wps = c.take<double>((int64_t)3 * (N - 1) * ld); L.gP = c.take<double>((int64_t)3 * (N - 1) * ld);
+  L.gT = c.take<double>((int64_t)N * ld); L.norm = c.take<double>((int64_t)3 * (N - 1) * ld);
+  L.doubles = c.doubles();
+  return L;
+}
+// Overlap enumeration of a corridor: the (N-1) B stacked pairs of 2 M rows | their vertices, K each | count | status (int32)
+struct SfcOverlapWs { double *stacked, *verts; int32_t *count, *status; int64_t doubles; };
+inline SfcOverlapWs sfc_overlap_ws(double *w, int N, int64_t B, int M, int K) {
+  Cursor c(w);
+  SfcOverlapWs L{};
+  const int64_t P = (int64_t)(N - 1) * B;
+  L.stacked = c.take<double>(P * 2 * M * 4); L.verts = c.take<double>(P * K * 3);
+  L.count = c.take<int32_t>(P); L.status = c.take<int32_t>(P);
+  L.doubles = c.doubles();
+  return L;
+}
+// backward_p: the L-BFGS state of the (N-1) ld problems of K variables (mem_size 8, past 3)
+constexpr int kSfcTinyMem = 8, kSfcTinyPast = 3;
+inline LbfgsLayout sfc_backward_p_ws(double *w, int N, int K, int64_t ld) {
+  return lbfgs_layout(w, K, kSfcTinyMem, kSfcTinyPast, (int64_t)(N - 1) * ld);
+}
+
 // status | iterations | evaluations of an L-BFGS run (k_lbfgs_results), int32 rows of ld
 struct LbfgsResultRows { int32_t *status, *iters, *evals; int64_t doubles; };
 inline LbfgsResultRows lbfgs_result_rows(double *w, int64_t ld) {

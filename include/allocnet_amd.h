@@ -909,6 +909,64 @@ int anet_comm_allgather_costs_dev(anet_ctx *ctx, const double *send, double *rec
                                   void *stream);
 int anet_comm_destroy(anet_ctx *ctx);
 
+/* ---- corridor-constrained MINCO L-BFGS: waypoints as vertex weights of corridor overlaps ---------- */
+/* Waypoint w (0 .. N-2) of a problem is a convex combination of the vertices v_0 .. v_{k-1} of overlap(polytope w, polytope
+ * w + 1), padded with zero rows to max_verts = K: P_w = (sum_j xi_j^2 v_j) / S, S = sum_j xi_j^2, with K free variables xi per
+ * waypoint (upstream GCOPTER's forwardP; allocnet_amd/csrc/sfc_param_kernels.h states the transform, its gradient, the norm
+ * restriction w_norm max(S - 1, 0)^3 and the inverse once).  Every iterate of the optimiser over (xi, tau) so has its junctions
+ * inside both polytopes they join.  Device arrays are batch-minor with the common row stride ld:
+ *   xi [(N-1) K][ld], row w K + j;  verts [(N-1) K 3][ld], row (w K + j) 3 + a;  count, status [(N-1)][ld] int32;
+ *   wps, grad_p [3 (N-1)][ld], row 3 w + a (what anet_minco_cost_grad_dev takes and returns);  norm [3 (N-1)][ld]: rows w hold
+ *   1 / S, rows (N-1) + w the norm cost of waypoint w, rows 2 (N-1) + w its gradient factor 6 w_norm max(S - 1, 0)^2.
+ * anet_sfc_overlap_vertices_dev: hpolys [N poly_rows 4][ld] as for anet_minco_cost_grad_dev (a.x <= b, zero rows padding),
+ * 2 poly_rows <= 128; the (N-1) batch stacked pairs go through anet_polytope_vertices_dev (same epsilon, same order of the
+ * vertices).  status: ANET_POLYTOPE_OK, _SKIPPED (no interior: count 0) or _TRUNCATED (more than max_verts vertices: the first
+ * max_verts are kept -- still a convex subset of the overlap -- and count is clamped to max_verts).  Slots behind count are zero.
+ * work: anet_sfc_overlap_workspace() doubles.
+ * anet_sfc_forward_p_dev: xi -> wps, norm.  anet_sfc_backward_grad_p_dev: grad_xi_j = 2 xi_j ((v_j - P_w) . grad_p_w) / S + the
+ * norm term, from the wps and norm rows the forward call left; cost ([ld] or NULL): the problem's norm costs are added to it.
+ * anet_sfc_backward_p_dev: xi of unit norm per waypoint minimising |P_w(xi) - wps_w|^2 from the vertex mean (L-BFGS, mem_size 8,
+ * g_epsilon 0, past 3, delta 1e-16, at most 200 evaluations) and residual [(N-1)][ld] = |P_w(xi) - wps_w|: positive for a point
+ * outside the overlap, +inf (xi = 0) for a waypoint without vertices.  work: anet_sfc_backward_p_workspace() doubles.          */
+int64_t anet_sfc_overlap_workspace(int n_pieces, int64_t batch, int poly_rows, int max_verts);
+int anet_sfc_overlap_vertices_dev(anet_ctx *ctx, int n_pieces, int64_t batch, int64_t ld, int poly_rows, const double *hpolys,
+                                  double epsilon, int max_verts, double *verts, int32_t *count, int32_t *status, double *work,
+                                  void *stream);
+int anet_sfc_forward_p_dev(anet_ctx *ctx, int n_pieces, int64_t batch, int64_t ld, int max_verts, const double *xi,
+                           const double *verts, double w_norm, double *wps, double *norm, void *stream);
+int anet_sfc_backward_grad_p_dev(anet_ctx *ctx, int n_pieces, int64_t batch, int64_t ld, int max_verts, const double *xi,
+                                 const double *verts, const double *wps, const double *norm, const double *grad_p,
+                                 double *grad_xi, double *cost, void *stream);
+int64_t anet_sfc_backward_p_workspace(int n_pieces, int max_verts, int64_t ld);
+int anet_sfc_backward_p_dev(anet_ctx *ctx, int n_pieces, int64_t batch, int64_t ld, int max_verts, const double *verts,
+                            const int32_t *count, const double *wps, double *xi, double *residual, double *work, void *stream);
+
+/* anet_lbfgs_minco_dev over x = (xi rows, tau rows), n = (N-1) max_verts + (N with ANET_OPT_TIMES): the lockstep shape
+ * (ANET_OPT_LOCKSTEP is implied), each evaluation forward_p -> cost + gradient -> backward_grad_p.  xi and T are read and written
+ * in place (start in, result out); wps_out [3 (N-1)][ld] receives P(xi) of the final iterate, coeffs_out (or NULL) its
+ * coefficients.  count / overlap_status ([(N-1)][ld], the latter may be NULL) are anet_sfc_overlap_vertices_dev's.  A problem
+ * with a waypoint of count < 2 or overlap status ANET_POLYTOPE_SKIPPED does not run: status ANET_SFC_NO_OVERLAP, zero counters,
+ * cost NaN, xi and T untouched.  min_duration and the cancel word as for anet_lbfgs_minco_bounded_dev.  The cost includes the
+ * norm restriction (0 while every S <= 1).  work: anet_sfc_workspace() doubles.                                                */
+#define ANET_SFC_NO_OVERLAP (-2048)
+int64_t anet_sfc_workspace(int s, int n_pieces, int max_verts, int64_t ld, const anet_lbfgs_params *params);
+int anet_lbfgs_minco_sfc_dev(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batch, int64_t ld, const double *head,
+                             const double *tail, double *xi, double *T, const double *verts, const int32_t *count,
+                             const int32_t *overlap_status, int max_verts, const double *hpolys, const anet_penalty *pen,
+                             const anet_lbfgs_params *params, int opt_flags, int max_evals, double min_duration, double w_norm,
+                             double *work, double *cost, double *wps_out, double *coeffs_out, int32_t *status, int32_t *iters,
+                             int32_t *evals, void *stream);
+/* The host-staged form: hpolys [batch][N][poly_rows][4] (pen->poly_rows; pen is required), wps_start [batch][N-1][3] or NULL
+ * (NULL: every waypoint starts at the mean of its overlap's vertices).  Enumerates the overlaps (epsilon), runs backward_p on
+ * the start waypoints, then the optimisation.  Out: wps_out [batch][N-1][3], T in place, cost, coeffs_out [batch][N][3][2s] or
+ * NULL, status / iters / evals, residual [batch][N-1] (backward_p's distances; 0 with wps_start NULL), overlap_status
+ * [batch][N-1] and xi_out [batch][(N-1) max_verts] (each may be NULL).                                                          */
+int anet_lbfgs_minco_sfc(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batch, const double *head, const double *tail,
+                         const double *wps_start, double *T, const double *hpolys, const anet_penalty *pen,
+                         const anet_lbfgs_params *params, int opt_flags, int max_evals, double min_duration, double w_norm,
+                         double epsilon, int max_verts, double *wps_out, double *cost, double *coeffs_out, int32_t *status,
+                         int32_t *iters, int32_t *evals, double *residual, int32_t *overlap_status, double *xi_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,219 @@
+// Corridor-constrained MINCO optimisation in upstream GCOPTER's shape (gcopter.hpp: forwardP / backwardP / backwardGradP and the
+// L-BFGS over (xi, tau)): every waypoint a convex combination of the vertices of the overlap of the two polytopes it joins,
+//     P_w = (sum_j xi_j^2 v_j) / sum_j xi_j^2,
+// so every iterate of the optimiser has its junctions inside the corridor.  The transform, its gradient, the norm restriction and
+// the inverse are stated once, in allocnet_amd/csrc/sfc_param_kernels.h; everything here is a batch of one through the C ABI
+// (anet_sfc_*, anet_lbfgs_minco_sfc in allocnet_amd.h), where the batch-minor device layout is the plain one:
+//     xi [(N-1) K], row w K + j;   vertices [(N-1) K][3];   waypoints [(N-1)][3].
+// Polytopes are GCOPTER's raw form, rows h with h.[x;1] <= 0, as everywhere in these headers; matrix arguments are duck-typed
+// ((r, c) access and rows()): Eigen types work unchanged and <Eigen/Eigen> is not needed.  The weight of v_0 is an ordinary entry
+// of xi here (upstream keeps v_0 and the edges v_j - v_0 and carries its weight last): K variables per waypoint, K the common
+// padded vertex count.
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "core.hpp"
+#include "lbfgs.hpp"
+#include "trajectory.hpp"
+
+namespace sfc_opt {
+
+// the vertices of the N - 1 overlaps of a corridor, padded to K per overlap (slots behind count[w] are zero)
+struct OverlapVertices {
+  int N = 0, K = 0;
+  std::vector<double> verts;            // [(N-1) K][3]
+  std::vector<int32_t> count, status;   // [(N-1)]: status ANET_POLYTOPE_OK / _SKIPPED (no interior) / _TRUNCATED (to K)
+};
+
+namespace detail {
+struct DevBuf {
+  double *p = nullptr;
+  size_t n = 0;
+  DevBuf(anet::Context &ctx, size_t count) : n(count ? count : 1) { ctx.check(anet_dev_alloc(ctx.get(), n, &p)); }
+  DevBuf(anet::Context &ctx, const std::vector<double> &h) : n(h.size() ? h.size() : 1) {
+    ctx.check(anet_dev_alloc(ctx.get(), n, &p));
+    if (!h.empty()) ctx.check(anet_dev_upload(ctx.get(), p, h.data(), h.size()));
+  }
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { anet_dev_free(p); }
+  void download(anet::Context &ctx, std::vector<double> &h) {
+    if (!h.empty()) ctx.check(anet_dev_download(ctx.get(), h.data(), p, h.size()));
+  }
+};
+// int32 rows travel in buffers of doubles, two per double
+inline std::vector<double> pack_i32(const std::vector<int32_t> &v) {
+  std::vector<double> d((v.size() + 1) / 2, 0.0);
+  if (!v.empty()) std::memcpy(d.data(), v.data(), v.size() * sizeof(int32_t));
+  return d;
+}
+inline void unpack_i32(const std::vector<double> &d, std::vector<int32_t> &v) {
+  if (!v.empty()) std::memcpy(v.data(), d.data(), v.size() * sizeof(int32_t));
+}
+// hPolys (raw form) -> [N][M][4] rows a.x <= b, zero rows as padding; M = the largest row count
+template <class Polys>
+inline std::vector<double> planner_form(const Polys &hPolys, int &M) {
+  const int N = (int)hPolys.size();
+  M = 1;
+  for (int i = 0; i < N; ++i) M = (int)hPolys[i].rows() > M ? (int)hPolys[i].rows() : M;
+  std::vector<double> hp((size_t)N * M * 4, 0.0);
+  for (int i = 0; i < N; ++i)
+    for (int r = 0; r < (int)hPolys[i].rows(); ++r) {
+      double *row = &hp[((size_t)i * M + r) * 4];
+      for (int c = 0; c < 3; ++c) row[c] = hPolys[i](r, c);
+      row[3] = -hPolys[i](r, 3);
+    }
+  return hp;
+}
+}  // namespace detail
+
+// anet_sfc_overlap_vertices_dev on one corridor (a container of raw-form polytopes with size() and [i]); maxVerts: K
+template <class Polys>
+inline OverlapVertices overlapVertices(const Polys &hPolys, const int maxVerts, const double epsilon = 1.0e-6) {
+  OverlapVertices ov;
+  ov.N = (int)hPolys.size();
+  ov.K = maxVerts;
+  int M = 1;
+  const std::vector<double> hp = detail::planner_form(hPolys, M);
+  const size_t nw = (size_t)(ov.N - 1);
+  ov.verts.assign(nw * ov.K * 3, 0.0);
+  ov.count.assign(nw, 0);
+  ov.status.assign(nw, 0);
+  anet::Context &ctx = anet::Context::thread_default();
+  const int64_t nwork = anet_sfc_overlap_workspace(ov.N, 1, M, ov.K);
+  if (nwork < 0) throw anet::Error(ANET_ERR_INVALID, "sfc_opt::overlapVertices: bad shape");
+  detail::DevBuf d_hp(ctx, hp), d_v(ctx, ov.verts.size()), d_c(ctx, (nw + 1) / 2), d_s(ctx, (nw + 1) / 2), work(ctx, (size_t)nwork);
+  ctx.check(anet_sfc_overlap_vertices_dev(ctx.get(), ov.N, 1, 1, M, d_hp.p, epsilon, ov.K, d_v.p, (int32_t *)d_c.p, (int32_t *)d_s.p,
+                                          work.p, anet_stream(ctx.get())));
+  std::vector<double> c((nw + 1) / 2), s((nw + 1) / 2);
+  d_v.download(ctx, ov.verts);
+  d_c.download(ctx, c);
+  d_s.download(ctx, s);
+  detail::unpack_i32(c, ov.count);
+  detail::unpack_i32(s, ov.status);
+  return ov;
+}
+
+// P = forwardP(xi): xi [(N-1) K] -> P [(N-1)][3]
+inline void forwardP(const std::vector<double> &xi, const OverlapVertices &ov, std::vector<double> &P) {
+  const size_t nw = (size_t)(ov.N - 1);
+  P.assign(nw * 3, 0.0);
+  anet::Context &ctx = anet::Context::thread_default();
+  detail::DevBuf d_xi(ctx, xi), d_v(ctx, ov.verts), d_p(ctx, P.size()), d_n(ctx, nw * 3);
+  ctx.check(anet_sfc_forward_p_dev(ctx.get(), ov.N, 1, 1, ov.K, d_xi.p, d_v.p, 1.0, d_p.p, d_n.p, anet_stream(ctx.get())));
+  d_p.download(ctx, P);
+}
+
+// gradXi = backwardGradP(xi, gradP): dJ/dxi [(N-1) K] from dJ/dP [(N-1)][3], the norm restriction's gradient (wNorm) included
+inline void backwardGradP(const std::vector<double> &xi, const OverlapVertices &ov, const std::vector<double> &gradP,
+                          std::vector<double> &gradXi, const double wNorm = 1.0) {
+  const size_t nw = (size_t)(ov.N - 1);
+  gradXi.assign(xi.size(), 0.0);
+  anet::Context &ctx = anet::Context::thread_default();
+  detail::DevBuf d_xi(ctx, xi), d_v(ctx, ov.verts), d_p(ctx, nw * 3), d_n(ctx, nw * 3), d_gp(ctx, gradP), d_g(ctx, gradXi.size());
+  ctx.check(anet_sfc_forward_p_dev(ctx.get(), ov.N, 1, 1, ov.K, d_xi.p, d_v.p, wNorm, d_p.p, d_n.p, anet_stream(ctx.get())));
+  ctx.check(anet_sfc_backward_grad_p_dev(ctx.get(), ov.N, 1, 1, ov.K, d_xi.p, d_v.p, d_p.p, d_n.p, d_gp.p, d_g.p, nullptr,
+                                         anet_stream(ctx.get())));
+  d_g.download(ctx, gradXi);
+}
+
+// xi = backwardP(P): unit-norm xi per waypoint with forwardP(xi) nearest to P, and the distances left (positive for a point
+// outside its overlap; the minimiser is not unique for more than four vertices: forwardP(xi) and the residual are the results)
+inline void backwardP(const std::vector<double> &P, const OverlapVertices &ov, std::vector<double> &xi, std::vector<double> &residual) {
+  const size_t nw = (size_t)(ov.N - 1);
+  xi.assign(nw * ov.K, 0.0);
+  residual.assign(nw, 0.0);
+  anet::Context &ctx = anet::Context::thread_default();
+  const int64_t nwork = anet_sfc_backward_p_workspace(ov.N, ov.K, 1);
+  if (nwork < 0) throw anet::Error(ANET_ERR_INVALID, "sfc_opt::backwardP: bad shape");
+  detail::DevBuf d_v(ctx, ov.verts), d_c(ctx, detail::pack_i32(ov.count)), d_p(ctx, P), d_xi(ctx, xi.size()), d_r(ctx, nw),
+      work(ctx, (size_t)nwork);
+  ctx.check(anet_sfc_backward_p_dev(ctx.get(), ov.N, 1, 1, ov.K, d_v.p, (const int32_t *)d_c.p, d_p.p, d_xi.p, d_r.p, work.p,
+                                    anet_stream(ctx.get())));
+  d_xi.download(ctx, xi);
+  d_r.download(ctx, residual);
+}
+
+// what optimize() reports besides the trajectory
+struct Result {
+  int status = 0, iters = 0, evals = 0;   // lbfgs_optimize's return value (or ANET_SFC_NO_OVERLAP), k, objective evaluations
+  double cost = 0.0;
+  int maxVerts = 0;
+  std::vector<double> wps;                // [(N-1)][3], inside both polytopes they join
+  std::vector<double> residual;           // [(N-1)]: how far backwardP's start is from the given waypoints
+  std::vector<int32_t> overlapStatus;     // [(N-1)]
+};
+
+// The corridor-constrained spatial-temporal optimisation of one trajectory (anet_lbfgs_minco_sfc): S = 3 (min-jerk,
+// Trajectory<5>) or 4 (min-snap, Trajectory<7>).  headState / tailState 3 x bcCols (columns p, v, a[, j]); hPolys: the N raw-form
+// polytopes; times: the N start durations ((i) access); inPs: 3 x (N-1) start waypoints, or nullptr to start every waypoint at
+// the mean of its overlap's vertices.  maxVerts 0: the next multiple of 8 above the largest overlap count.
+template <int S, class M1, class M2, class Polys, class VT, class MP = anet::MatrixX>
+inline Trajectory<2 * S - 1> optimize(const M1 &headState, const M2 &tailState, const Polys &hPolys, const VT &times,
+                                      const anet_penalty &penalty, const lbfgs::lbfgs_parameter_t &param, Result *result = nullptr,
+                                      const MP *inPs = nullptr, const int bcCols = 3, const int maxEvals = 2000,
+                                      const double minDuration = 0.0, const double wNorm = 1.0, int maxVerts = 0,
+                                      const double epsilon = 1.0e-6) {
+  const int N = (int)hPolys.size(), c = bcCols;
+  int M = 1;
+  const std::vector<double> hp = detail::planner_form(hPolys, M);
+  std::vector<double> head((size_t)3 * c), tail((size_t)3 * c), T((size_t)N), w0;
+  for (int a = 0; a < 3; ++a)
+    for (int j = 0; j < c; ++j) {
+      head[(size_t)a * c + j] = headState(a, j);
+      tail[(size_t)a * c + j] = tailState(a, j);
+    }
+  for (int i = 0; i < N; ++i) T[i] = times(i);
+  if (inPs) {
+    w0.resize((size_t)3 * (N - 1));
+    for (int k = 0; k + 1 < N; ++k)
+      for (int a = 0; a < 3; ++a) w0[(size_t)k * 3 + a] = (*inPs)(a, k);
+  }
+  anet::Context &ctx = anet::Context::thread_default();
+  if (maxVerts <= 0) {  // one enumeration that only counts: room for one vertex reports the true counts
+    int most = 0;
+    for (int w = 0; w + 1 < N; ++w) {
+      std::vector<double> rows;
+      for (int q = 0; q < 2; ++q)
+        for (int r = 0; r < M; ++r) {
+          const double *row = &hp[((size_t)(w + q) * M + r) * 4];
+          rows.insert(rows.end(), {row[0], row[1], row[2], -row[3]});
+        }
+      double one[3];
+      int32_t count = 0;
+      ctx.check(anet_polytope_vertices(ctx.get(), 1, 2 * M, rows.data(), epsilon, 1, one, &count, nullptr, nullptr));
+      most = count > most ? count : most;
+    }
+    maxVerts = (most / 8 + 1) * 8;
+  }
+  anet_penalty pen = penalty;
+  pen.poly_rows = M;
+  const anet_lbfgs_params prm = lbfgs::to_c(param);
+  Result local;
+  Result &R = result ? *result : local;
+  R.maxVerts = maxVerts;
+  R.wps.assign((size_t)3 * (N - 1), 0.0);
+  R.residual.assign((size_t)(N - 1), 0.0);
+  R.overlapStatus.assign((size_t)(N - 1), 0);
+  std::vector<double> coeffs((size_t)N * 3 * 2 * S);
+  int32_t status = 0, iters = 0, evals = 0;
+  ctx.check(anet_lbfgs_minco_sfc(ctx.get(), S, c, N, 1, head.data(), tail.data(), inPs ? w0.data() : nullptr, T.data(), hp.data(), &pen,
+                                 &prm, ANET_OPT_WAYPOINTS | ANET_OPT_TIMES, maxEvals, minDuration, wNorm, epsilon, maxVerts,
+                                 R.wps.data(), &R.cost, coeffs.data(), &status, &iters, &evals, R.residual.data(),
+                                 R.overlapStatus.data(), nullptr));
+  R.status = status; R.iters = iters; R.evals = evals;
+  Trajectory<2 * S - 1> traj;
+  traj.reserve(N);
+  for (int i = 0; i < N; ++i) {
+    anet::Matrix<3, 2 * S> cm;
+    for (int a = 0; a < 3; ++a)
+      for (int k = 0; k < 2 * S; ++k) cm(a, k) = coeffs[((size_t)i * 3 + a) * 2 * S + k];
+    traj.emplace_back(T[i], cm);
+  }
+  return traj;
+}
+
+}  // namespace sfc_opt
