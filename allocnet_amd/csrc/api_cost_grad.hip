@@ -258,22 +258,15 @@ int anet_minco_cost_grad(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batc
   const int64_t nco = (int64_t)N * 3 * 2 * s;
   const int64_t M = (pen && hpolys) ? pen->poly_rows : 0;
   const int64_t nhp = (int64_t)N * M * 4;
-  const int64_t n_in = 6 * (int64_t)c + (int64_t)(N - 1) * 3 + N + nhp;
-  const int64_t n_out = 1 + (int64_t)(N - 1) * 3 + N + nco;
-  int64_t mx = nco > nhp ? nco : nhp;
-  if (mx < 3 * (int64_t)c) mx = 3 * c;
-  Stager st;
-  rc = make_stager(ctx, batch, mx, n_in + n_out + anet_minco_cost_grad_workspace(s, N, 1), &st);
+  Stager st(ctx, batch);
+  double *d_head, *d_tail, *d_wps, *d_T, *d_hp = nullptr, *d_cost, *d_gP, *d_gT, *d_co, *d_work;
+  rc = st.stage([&](Stager::Pass &p) {
+    p.in(head, 3 * c, &d_head); p.in(tail, 3 * c, &d_tail); p.in(wps, (int64_t)(N - 1) * 3, &d_wps); p.in(T, N, &d_T);
+    if (nhp) p.in(hpolys, nhp, &d_hp);
+    p.rows(1, &d_cost); p.out((int64_t)(N - 1) * 3, &d_gP); p.out(N, &d_gT); p.out(nco, &d_co);
+    p.doubles(anet_minco_cost_grad_workspace(s, N, st.ld), &d_work);
+  });
   if (rc) return rc;
-  double *d_head, *d_tail, *d_wps, *d_T, *d_hp = nullptr;
-  if ((rc = st.upload(head, 3 * c, &d_head))) return rc;
-  if ((rc = st.upload(tail, 3 * c, &d_tail))) return rc;
-  if ((rc = st.upload(wps, (int64_t)(N - 1) * 3, &d_wps))) return rc;
-  if ((rc = st.upload(T, N, &d_T))) return rc;
-  if (nhp && (rc = st.upload(hpolys, nhp, &d_hp))) return rc;
-  double *d_cost = st.reserve(1), *d_gP = st.reserve((int64_t)(N - 1) * 3), *d_gT = st.reserve(N);
-  double *d_co = st.reserve(nco);
-  double *d_work = st.reserve(anet_minco_cost_grad_workspace(s, N, 1));
   rc = anet_minco_cost_grad_dev(ctx, s, c, N, batch, st.ld, d_head, d_tail, d_wps, d_T, d_hp, pen, d_work,
                                 d_cost, d_gP, d_gT, d_co, ctx->stream);
   if (rc) return rc;

@@ -146,15 +146,15 @@ int anet_flat_forward(anet_ctx *ctx, const anet_flat_params *params, int64_t bat
   if (batch < 0) return fail(ctx, ANET_ERR_INVALID, "negative batch");
   if (batch == 0) return ANET_OK;
   if (!vel || !acc || !jer || !thr || !quat || !omg) return fail(ctx, ANET_ERR_INVALID, "anet_flat_forward: NULL pointer");
-  Stager st;
-  if ((rc = make_stager(ctx, batch, 4, 11 + 8, &st))) return rc;
-  double *d_v, *d_a, *d_j, *d_psi = nullptr, *d_dpsi = nullptr;
-  if ((rc = st.upload(vel, 3, &d_v))) return rc;
-  if ((rc = st.upload(acc, 3, &d_a))) return rc;
-  if ((rc = st.upload(jer, 3, &d_j))) return rc;
-  if (psi && (rc = st.upload(psi, 1, &d_psi))) return rc;
-  if (dpsi && (rc = st.upload(dpsi, 1, &d_dpsi))) return rc;
-  double *d_thr = st.reserve(1), *d_q = st.reserve(4), *d_o = st.reserve(3);
+  Stager st(ctx, batch);
+  double *d_v, *d_a, *d_j, *d_psi = nullptr, *d_dpsi = nullptr, *d_thr, *d_q, *d_o;
+  rc = st.stage([&](Stager::Pass &p) {
+    p.in(vel, 3, &d_v); p.in(acc, 3, &d_a); p.in(jer, 3, &d_j);
+    if (psi) p.in(psi, 1, &d_psi);
+    if (dpsi) p.in(dpsi, 1, &d_dpsi);
+    p.out(1, &d_thr); p.out(4, &d_q); p.out(3, &d_o);
+  });
+  if (rc) return rc;
   rc = anet_flat_forward_dev(ctx, params, batch, st.ld, d_v, d_a, d_j, d_psi, d_dpsi, d_thr, d_q, d_o, ctx->stream);
   if (rc) return rc;
   if ((rc = st.download(d_thr, 1, thr))) return rc;
@@ -173,21 +173,19 @@ int anet_flat_backward(anet_ctx *ctx, const anet_flat_params *params, int64_t ba
   if (batch == 0) return ANET_OK;
   if (!vel || !acc || !jer || !thr_grad || !quat_grad || !omg_grad || !vel_total || !acc_total || !jer_total)
     return fail(ctx, ANET_ERR_INVALID, "anet_flat_backward: NULL pointer");
-  Stager st;
-  if ((rc = make_stager(ctx, batch, 4, 11 + 14 + 14, &st))) return rc;
+  Stager st(ctx, batch);
   double *d_v, *d_a, *d_j, *d_psi = nullptr, *d_dpsi = nullptr, *d_pg = nullptr, *d_vg = nullptr, *d_tg, *d_qg, *d_og;
-  if ((rc = st.upload(vel, 3, &d_v))) return rc;
-  if ((rc = st.upload(acc, 3, &d_a))) return rc;
-  if ((rc = st.upload(jer, 3, &d_j))) return rc;
-  if (psi && (rc = st.upload(psi, 1, &d_psi))) return rc;
-  if (dpsi && (rc = st.upload(dpsi, 1, &d_dpsi))) return rc;
-  if (pos_grad && (rc = st.upload(pos_grad, 3, &d_pg))) return rc;
-  if (vel_grad && (rc = st.upload(vel_grad, 3, &d_vg))) return rc;
-  if ((rc = st.upload(thr_grad, 1, &d_tg))) return rc;
-  if ((rc = st.upload(quat_grad, 4, &d_qg))) return rc;
-  if ((rc = st.upload(omg_grad, 3, &d_og))) return rc;
-  double *d_pt = st.reserve(3), *d_vt = st.reserve(3), *d_at = st.reserve(3), *d_jt = st.reserve(3), *d_pst = st.reserve(1),
-         *d_dpt = st.reserve(1);
+  double *d_pt, *d_vt, *d_at, *d_jt, *d_pst, *d_dpt;
+  rc = st.stage([&](Stager::Pass &p) {
+    p.in(vel, 3, &d_v); p.in(acc, 3, &d_a); p.in(jer, 3, &d_j);
+    if (psi) p.in(psi, 1, &d_psi);
+    if (dpsi) p.in(dpsi, 1, &d_dpsi);
+    if (pos_grad) p.in(pos_grad, 3, &d_pg);
+    if (vel_grad) p.in(vel_grad, 3, &d_vg);
+    p.in(thr_grad, 1, &d_tg); p.in(quat_grad, 4, &d_qg); p.in(omg_grad, 3, &d_og);
+    p.out(3, &d_pt); p.out(3, &d_vt); p.out(3, &d_at); p.out(3, &d_jt); p.out(1, &d_pst); p.out(1, &d_dpt);
+  });
+  if (rc) return rc;
   rc = anet_flat_backward_dev(ctx, params, batch, st.ld, d_v, d_a, d_j, d_psi, d_dpsi, d_pg, d_vg, d_tg, d_qg, d_og, d_pt, d_vt,
                               d_at, d_jt, d_pst, d_dpt, ctx->stream);
   if (rc) return rc;
@@ -208,13 +206,10 @@ int anet_traj_flat_states(anet_ctx *ctx, const anet_flat_params *params, int s, 
   if (batch == 0 || nq <= 0) return nq < 0 ? fail(ctx, ANET_ERR_INVALID, "nq < 0") : ANET_OK;
   if (!coeffs || !T || !tq || !out) return fail(ctx, ANET_ERR_INVALID, "anet_traj_flat_states: NULL pointer");
   const int64_t nco = (int64_t)n_pieces * 3 * 2 * s, nout = (int64_t)nq * anet::kFlatStateFields;
-  Stager st;
-  if ((rc = make_stager(ctx, batch, nco > nout ? nco : nout, nco + n_pieces + nq + nout, &st))) return rc;
-  double *d_co, *d_T, *d_tq;
-  if ((rc = st.upload(coeffs, nco, &d_co))) return rc;
-  if ((rc = st.upload(T, n_pieces, &d_T))) return rc;
-  if ((rc = st.upload(tq, nq, &d_tq))) return rc;
-  double *d_out = st.reserve(nout);
+  Stager st(ctx, batch);
+  double *d_co, *d_T, *d_tq, *d_out;
+  rc = st.stage([&](Stager::Pass &p) { p.in(coeffs, nco, &d_co); p.in(T, n_pieces, &d_T); p.in(tq, nq, &d_tq); p.out(nout, &d_out); });
+  if (rc) return rc;
   rc = anet_traj_flat_states_dev(ctx, params, s, n_pieces, batch, st.ld, d_co, d_T, nq, d_tq, d_out, ctx->stream);
   if (rc) return rc;
   return st.download(d_out, nout, out);
@@ -229,12 +224,10 @@ int anet_traj_flat_extrema(anet_ctx *ctx, const anet_flat_params *params, int s,
   if (batch == 0) return ANET_OK;
   if (!coeffs || !T || !out) return fail(ctx, ANET_ERR_INVALID, "anet_traj_flat_extrema: NULL pointer");
   const int64_t nco = (int64_t)n_pieces * 3 * 2 * s;
-  Stager st;
-  if ((rc = make_stager(ctx, batch, nco, nco + n_pieces + 4, &st))) return rc;
-  double *d_co, *d_T;
-  if ((rc = st.upload(coeffs, nco, &d_co))) return rc;
-  if ((rc = st.upload(T, n_pieces, &d_T))) return rc;
-  double *d_out = st.reserve(4);
+  Stager st(ctx, batch);
+  double *d_co, *d_T, *d_out;
+  rc = st.stage([&](Stager::Pass &p) { p.in(coeffs, nco, &d_co); p.in(T, n_pieces, &d_T); p.out(4, &d_out); });
+  if (rc) return rc;
   rc = anet_traj_flat_extrema_dev(ctx, params, s, n_pieces, batch, st.ld, d_co, d_T, res, d_out, ctx->stream);
   if (rc) return rc;
   return st.download(d_out, 4, out);

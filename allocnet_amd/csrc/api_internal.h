@@ -29,7 +29,8 @@
 
 #include "../../include/allocnet_amd.h"
 #include "tuning.h"
-#include "workspace.h"  // the shape of every workspace and staging buffer: the only place one is written
+#include "workspace.h"  // the shape of every device workspace: the only place one is written
+#include "staging.h"    // the staging buffers of the host entry points: one statement each, measured and carved by the same code
 
 #pragma GCC visibility push(hidden)
 
@@ -195,85 +196,68 @@ inline int check_penalty(anet_ctx *ctx, const anet_penalty *pen) {
   return ANET_OK;
 }
 
-// Host (trajectory-major) wrappers: stage -> batch-minor -> kernel -> back.
-struct Stager {
+// Host (trajectory-major) wrappers: stage -> batch-minor -> kernel -> back.  The layout of the staging buffer, the pack of a single
+// trajectory and the width check of download() are staging.h's; this is its transport: the context's scratch, the pinned pack
+// buffer, the copies on the context's stream and the transpose kernels.
+// (the entry point that stages has made the context's device current: ANET_ON_DEVICE)
+struct HipStaging {
   anet_ctx *ctx;
-  int64_t batch, ld;
-  double *stage;   // batch * max_fields doubles
-  double *cursor;  // next free batch-minor region
-  int upload(const double *host, int64_t nf, double **dev) {
-    *dev = cursor;
-    cursor += nf * ld;
-    if (nf == 0) return ANET_OK;
-    if (batch == 1) {
-      // one trajectory: both layouts coincide (ld = 1), no transpose kernel; the inputs are packed into
-      // pinned memory and go out with a single copy when the first output region is reserved
-      if (!pack_base) pack_base = *dev;
-      const size_t off = (size_t)(*dev - pack_base);
-      if (off + (size_t)nf > ctx->h_pack_doubles) {
-        const size_t want = (off + (size_t)nf) * 2 + 1024;
-        double *np_ = nullptr;
-        hipError_t e1 = hipHostMalloc((void **)&np_, sizeof(double) * want, hipHostMallocDefault);
-        if (e1 != hipSuccess) return hip_fail(ctx, e1, "hipHostMalloc(pack)");
-        if (ctx->h_pack) {
-          memcpy(np_, ctx->h_pack, sizeof(double) * off);
-          (void)hipHostFree(ctx->h_pack);
-        }
-        ctx->h_pack = np_;
-        ctx->h_pack_doubles = want;
+  int scratch(int64_t bytes, void **base) { const int rc = ensure_scratch(ctx, (size_t)bytes); *base = ctx->scratch; return rc; }
+  int pack(int64_t off, const double *host, int64_t nf) {
+    if ((size_t)(off + nf) > ctx->h_pack_doubles) {
+      const size_t want = (size_t)(off + nf) * 2 + 1024;
+      double *np_ = nullptr;
+      hipError_t e1 = hipHostMalloc((void **)&np_, sizeof(double) * want, hipHostMallocDefault);
+      if (e1 != hipSuccess) return hip_fail(ctx, e1, "hipHostMalloc(pack)");
+      if (ctx->h_pack) {
+        memcpy(np_, ctx->h_pack, sizeof(double) * off);
+        (void)hipHostFree(ctx->h_pack);
       }
-      memcpy(ctx->h_pack + off, host, sizeof(double) * nf);
-      pack_doubles = off + (size_t)nf;
-      return ANET_OK;
+      ctx->h_pack = np_;
+      ctx->h_pack_doubles = want;
     }
-    hipError_t e = hipMemcpyAsync(stage, host, sizeof(double) * batch * nf, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "hipMemcpyAsync(H2D)");
-    return anet_to_batch_minor_dev(ctx, batch, nf, ld, stage, *dev, ctx->stream);
-  }
-  double *pack_base = nullptr;
-  size_t pack_doubles = 0;
-  int flush() {  // send the packed single-trajectory inputs (no-op otherwise)
-    if (pack_base && pack_doubles) {
-      hipError_t e = hipMemcpyAsync(pack_base, ctx->h_pack, sizeof(double) * pack_doubles, hipMemcpyHostToDevice, ctx->stream);
-      pack_doubles = 0;
-      if (e != hipSuccess) return hip_fail(ctx, e, "hipMemcpyAsync(H2D packed)");
-    }
+    memcpy(ctx->h_pack + off, host, sizeof(double) * nf);
     return ANET_OK;
   }
-  double *reserve(int64_t nf) {  // called after all uploads and before the kernels in every entry point
-    (void)flush();
-    double *p = cursor;
-    cursor += nf * ld;
-    return p;
+  const double *packed() const { return ctx->h_pack; }
+  int put(double *dev, const double *host, int64_t n) {
+    hipError_t e = hipMemcpyAsync(dev, host, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream);
+    return e == hipSuccess ? ANET_OK : hip_fail(ctx, e, "hipMemcpyAsync(H2D)");
   }
-  int download(const double *dev, int64_t nf, double *host) {
-    if (batch == 1) {
-      hipError_t e1 = hipMemcpyAsync(host, dev, sizeof(double) * nf, hipMemcpyDeviceToHost, ctx->stream);
-      if (e1 != hipSuccess) return hip_fail(ctx, e1, "hipMemcpyAsync(D2H)");
-      e1 = hipStreamSynchronize(ctx->stream);
-      if (e1 != hipSuccess) return hip_fail(ctx, e1, "hipStreamSynchronize");
-      return ANET_OK;
-    }
-    int rc = anet_to_traj_major_dev(ctx, batch, nf, ld, dev, stage, ctx->stream);
-    if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(host, stage, sizeof(double) * batch * nf, hipMemcpyDeviceToHost, ctx->stream);
+  int scatter(const double *host, int64_t batch, int64_t nf, int64_t ld, double *area, double *dev) {
+    const int rc = put(area, host, batch * nf);
+    return rc ? rc : anet_to_batch_minor_dev(ctx, batch, nf, ld, area, dev, ctx->stream);
+  }
+  int fetch(const double *dev, int64_t n, double *host) {
+    hipError_t e = hipMemcpyAsync(host, dev, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "hipMemcpyAsync(D2H)");
-    // the staging buffer is reused by the next transfer
-    e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "hipStreamSynchronize");
-    return ANET_OK;
+    e = hipStreamSynchronize(ctx->stream);  // (the staging area is reused by the next transfer)
+    return e == hipSuccess ? ANET_OK : hip_fail(ctx, e, "hipStreamSynchronize");
   }
+  int gather(const double *dev, int64_t batch, int64_t nf, int64_t ld, double *area, double *host) {
+    const int rc = anet_to_traj_major_dev(ctx, batch, nf, ld, dev, area, ctx->stream);
+    return rc ? rc : fetch(area, batch * nf, host);
+  }
+  int refuse(const char *why) { return fail(ctx, ANET_ERR_INVALID, why); }
 };
-inline int make_stager(anet_ctx *ctx, int64_t batch, int64_t max_field, int64_t total_fields, Stager *st) {
-  // (the entry point that stages has made the context's device current: ANET_ON_DEVICE)
-  const int64_t ld = batch == 1 ? 1 : anet_recommended_ld(batch);
-  int rc = ensure_scratch(ctx, sizeof(double) * (size_t)(batch * max_field + total_fields * ld));
-  if (rc) return rc;
-  st->ctx = ctx; st->batch = batch; st->ld = ld;
-  st->stage = (double *)ctx->scratch;
-  st->cursor = st->stage + batch * max_field;
-  st->pack_base = nullptr;
-  st->pack_doubles = 0;
+struct Stager : anet::Staging<HipStaging> {
+  Stager(anet_ctx *ctx, int64_t batch) : Staging{{ctx}, batch, batch == 1 ? 1 : anet_recommended_ld(batch)} {}
+};
+
+// the parameter check of every L-BFGS entry point
+inline int check_lbfgs(anet_ctx *ctx, int n, const anet_lbfgs_params *params, int max_evals) {
+  const int code = anet_lbfgs_check_params(n, params);
+  if (code) return fail(ctx, ANET_ERR_INVALID, std::string("lbfgs parameters rejected: ") + anet_lbfgs_strerror(code));
+  if (max_evals <= 0) return fail(ctx, ANET_ERR_INVALID, "max_evals must be > 0");
+  return ANET_OK;
+}
+// the status / iters / evals rows k_lbfgs_results filled and the cost -> the caller's host arrays
+inline int download_results(anet_ctx *ctx, int64_t batch, const anet::LbfgsResultRows &r, const double *d_cost, int32_t *status,
+                            int32_t *iters, int32_t *evals, double *cost, hipStream_t s0) {
+  if (status) ANET_HIP(ctx, hipMemcpyAsync(status, r.status, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
+  if (iters) ANET_HIP(ctx, hipMemcpyAsync(iters, r.iters, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
+  if (evals) ANET_HIP(ctx, hipMemcpyAsync(evals, r.evals, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
+  if (cost) ANET_HIP(ctx, hipMemcpyAsync(cost, d_cost, sizeof(double) * batch, hipMemcpyDeviceToHost, s0));
   return ANET_OK;
 }
 

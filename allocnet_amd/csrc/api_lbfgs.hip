@@ -243,26 +243,6 @@ const char *anet_lbfgs_strerror(int code) {
   }
 }
 
-// the status / iters / evals rows k_lbfgs_results filled and the cost -> the caller's host arrays
-static int download_results(anet_ctx *ctx, int64_t batch, const anet::LbfgsResultRows &r, const double *d_cost, int32_t *status,
-                            int32_t *iters, int32_t *evals, double *cost, hipStream_t s0) {
-  if (status) ANET_HIP(ctx, hipMemcpyAsync(status, r.status, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
-  if (iters) ANET_HIP(ctx, hipMemcpyAsync(iters, r.iters, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
-  if (evals) ANET_HIP(ctx, hipMemcpyAsync(evals, r.evals, sizeof(int) * batch, hipMemcpyDeviceToHost, s0));
-  if (cost) ANET_HIP(ctx, hipMemcpyAsync(cost, d_cost, sizeof(double) * batch, hipMemcpyDeviceToHost, s0));
-  return ANET_OK;
-}
-
-// the result rows in a Stager's units: rows of ld doubles
-static int64_t result_row_fields(int64_t ld) { return (anet::lbfgs_result_rows(nullptr, ld).doubles + ld - 1) / ld; }
-
-static int check_lbfgs(anet_ctx *ctx, int n, const anet_lbfgs_params *params, int max_evals) {
-  const int code = anet_lbfgs_check_params(n, params);
-  if (code) return fail(ctx, ANET_ERR_INVALID, std::string("lbfgs parameters rejected: ") + anet_lbfgs_strerror(code));
-  if (max_evals <= 0) return fail(ctx, ANET_ERR_INVALID, "max_evals must be > 0");
-  return ANET_OK;
-}
-
 int anet_lbfgs_mvie(anet_ctx *ctx, int64_t batch, int M, const double *A, double smooth_eps,
                     double penalty_wt, double *x, double *f, const anet_lbfgs_params *params,
                     int max_evals, int32_t *status, int32_t *iters, int32_t *evals) {
@@ -273,17 +253,16 @@ int anet_lbfgs_mvie(anet_ctx *ctx, int64_t batch, int M, const double *A, double
   if (batch == 0) return ANET_OK;
   if (!A || !x) return fail(ctx, ANET_ERR_INVALID, "anet_lbfgs_mvie: NULL pointer");
   const int n = 9, m = params->mem_size, npf = params->past > 1 ? params->past : 1;
-  Stager st;
-  const int64_t wdoubles = anet::lbfgs_layout(nullptr, n, m, npf, 1).doubles;
-  const int64_t mx = 3 * (int64_t)M > n ? 3 * (int64_t)M : n;
-  const int64_t rfields = result_row_fields(batch == 1 ? 1 : anet_recommended_ld(batch));  // (the stager's row stride)
-  rc = make_stager(ctx, batch, mx, 3 * (int64_t)M + n + wdoubles + rfields, &st);
-  if (rc) return rc;
+  Stager st(ctx, batch);
   double *d_A, *d_x0;
-  if ((rc = st.upload(A, 3 * (int64_t)M, &d_A))) return rc;
-  if ((rc = st.upload(x, n, &d_x0))) return rc;
-  LbfgsLayout L = anet::lbfgs_layout(st.reserve(wdoubles), n, m, npf, st.ld);
-  const anet::LbfgsResultRows R = anet::lbfgs_result_rows(st.reserve(rfields), st.ld);
+  LbfgsLayout L;
+  anet::LbfgsResultRows R;
+  rc = st.stage([&](Stager::Pass &p) {
+    p.in(A, 3 * (int64_t)M, &d_A); p.in(x, n, &d_x0);  // (x comes back from L.x: the same width)
+    L = anet::lbfgs_layout(p.c, n, m, npf, st.ld);
+    R = anet::lbfgs_result_rows(p.c, st.ld);
+  });
+  if (rc) return rc;
   hipStream_t s0 = ctx->stream;
   ANET_HIP(ctx, hipMemcpyAsync(L.x, d_x0, sizeof(double) * n * st.ld, hipMemcpyDeviceToDevice, s0));
   anet::MvieArgs ma{d_A, L.x, L.feval, L.g, L.is, batch, st.ld, M, smooth_eps, penalty_wt};
@@ -702,25 +681,19 @@ static int lbfgs_minco_host_impl(anet_ctx *ctx, int s, int c, int n_pieces, int6
   const int64_t nco = (int64_t)N * 3 * 2 * s;
   const int64_t M = (pen && hpolys) ? pen->poly_rows : 0;
   const int64_t nhp = (int64_t)N * M * 4;
-  // (the workspace has terms that do not scale with ld: asked for with the stager's own row stride, reserved in rows of it)
-  const int64_t ld_h = batch == 1 ? 1 : anet_recommended_ld(batch);
-  const int64_t wtotal = anet_lbfgs_minco_workspace(s, N, ld_h, params);
+  Stager st(ctx, batch);
+  // (the workspace has terms that do not scale with ld: asked for with the stager's own row stride)
+  const int64_t wtotal = anet_lbfgs_minco_workspace(s, N, st.ld, params);
   if (wtotal < 0) return fail(ctx, ANET_ERR_INVALID, "anet_lbfgs_minco: bad lbfgs parameters");
-  const int64_t wdoubles = (wtotal + ld_h - 1) / ld_h;
-  int64_t mx = nco > nhp ? nco : nhp;
-  if (mx < 3 * (int64_t)c) mx = 3 * c;
-  Stager st;
-  const int64_t rfields = result_row_fields(ld_h);
-  rc = make_stager(ctx, batch, mx, 6 * (int64_t)c + 3 * (int64_t)(N - 1) + N + nhp + nco + wdoubles + 1 + rfields, &st);
+  double *d_head, *d_tail, *d_wps, *d_T, *d_hp = nullptr, *d_co, *d_work, *d_cost;
+  anet::LbfgsResultRows R;
+  rc = st.stage([&](Stager::Pass &p) {
+    p.in(head, 3 * c, &d_head); p.in(tail, 3 * c, &d_tail); p.in(wps, (int64_t)(N - 1) * 3, &d_wps); p.in(T, N, &d_T);
+    if (nhp) p.in(hpolys, nhp, &d_hp);
+    p.out(nco, &d_co); p.doubles(wtotal, &d_work); p.rows(1, &d_cost);
+    R = anet::lbfgs_result_rows(p.c, st.ld);
+  });
   if (rc) return rc;
-  double *d_head, *d_tail, *d_wps, *d_T, *d_hp = nullptr;
-  if ((rc = st.upload(head, 3 * c, &d_head))) return rc;
-  if ((rc = st.upload(tail, 3 * c, &d_tail))) return rc;
-  if ((rc = st.upload(wps, (int64_t)(N - 1) * 3, &d_wps))) return rc;
-  if ((rc = st.upload(T, N, &d_T))) return rc;
-  if (nhp && (rc = st.upload(hpolys, nhp, &d_hp))) return rc;
-  double *d_co = st.reserve(nco), *d_work = st.reserve(wdoubles), *d_cost = st.reserve(1);
-  const anet::LbfgsResultRows R = anet::lbfgs_result_rows(st.reserve(rfields), st.ld);
   rc = lbfgs_minco_dev_impl(ctx, s, c, N, batch, st.ld, d_head, d_tail, d_wps, d_T, d_hp, pen, params, opt_flags,
                             max_evals, min_duration, nullptr, d_work, d_cost, coeffs_out ? d_co : nullptr, R.status, R.iters, R.evals,
                             ctx->stream);

@@ -176,9 +176,7 @@ int anet_lbfgs_minco_sfc_dev(anet_ctx *ctx, int s, int c, int n_pieces, int64_t 
   if (!(min_duration >= 0.0) || !(w_norm >= 0.0)) return fail(ctx, ANET_ERR_INVALID, "anet_lbfgs_minco_sfc_dev: min_duration and w_norm must be >= 0");
   const int N = n_pieces, K = max_verts, nxi = (N - 1) * K, nt = (opt_flags & ANET_OPT_TIMES) ? N : 0, n = nxi + nt;
   if (!params) return fail(ctx, ANET_ERR_INVALID, "anet_lbfgs_minco_sfc_dev: params is NULL");
-  const int code = anet_lbfgs_check_params(n, params);
-  if (code) return fail(ctx, ANET_ERR_INVALID, std::string("lbfgs parameters rejected: ") + anet_lbfgs_strerror(code));
-  if (max_evals <= 0) return fail(ctx, ANET_ERR_INVALID, "max_evals must be > 0");
+  if ((rc = check_lbfgs(ctx, n, params, max_evals))) return rc;
   if (batch == 0) return ANET_OK;
   if (!head || !tail || !xi || !T || !verts || !count || !work || !wps_out)
     return fail(ctx, ANET_ERR_INVALID, "anet_lbfgs_minco_sfc_dev: NULL pointer");
@@ -227,38 +225,32 @@ int anet_lbfgs_minco_sfc(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batc
   const int N = n_pieces, K = max_verts, M = pen->poly_rows;
   if (M < 1) return fail(ctx, ANET_ERR_INVALID, "anet_lbfgs_minco_sfc: pen->poly_rows must be >= 1");
   const int64_t nco = (int64_t)N * 3 * 2 * s, nhp = (int64_t)N * M * 4, nwp = (int64_t)3 * (N - 1), nxi = (int64_t)(N - 1) * K;
-  const int64_t ld_h = batch == 1 ? 1 : anet_recommended_ld(batch);
-  const int64_t w_opt = anet_sfc_workspace(s, N, K, ld_h, params), w_ov = anet_sfc_overlap_workspace(N, batch, M, K),
-                w_bp = anet_sfc_backward_p_workspace(N, K, ld_h);
+  Stager sg(ctx, batch);
+  const int64_t ld = sg.ld;
+  const int64_t w_opt = anet_sfc_workspace(s, N, K, ld, params), w_ov = anet_sfc_overlap_workspace(N, batch, M, K),
+                w_bp = anet_sfc_backward_p_workspace(N, K, ld);
   if (w_opt < 0 || w_ov < 0 || w_bp < 0) return fail(ctx, ANET_ERR_INVALID, "anet_lbfgs_minco_sfc: bad lbfgs parameters or shape");
-  // the three workspaces are used one after the other: one region of the largest, in rows of the stager's stride
+  // the three workspaces are used one after the other: one region of the largest
   int64_t wmax = w_opt > w_ov ? w_opt : w_ov;
   if (w_bp > wmax) wmax = w_bp;
-  const int64_t wrows = (wmax + ld_h - 1) / ld_h, irows = (anet::lbfgs_result_rows(nullptr, ld_h).doubles + ld_h - 1) / ld_h;
-  // (the staging region in front of the stager's rows also keeps the enumeration's depths, (N - 1) batch doubles, while it runs)
-  int64_t mx = nco > nhp ? nco : nhp;
-  if (mx < nxi) mx = nxi;
-  if (mx < 3 * (int64_t)c) mx = 3 * c;
-  Stager sg;
-  rc = make_stager(ctx, batch, mx, 6 * (int64_t)c + nwp + N + nhp + nxi + 3 * nxi + 3 * (N - 1) + nwp + nco + 1 + wrows + irows, &sg);
+  double *d_head, *d_tail, *d_wp0 = nullptr, *d_T, *d_hp, *d_xi, *d_verts, *d_res, *d_wps, *d_co, *d_cost, *d_work;
+  int32_t *count, *ostat;
+  anet::LbfgsResultRows R;
+  rc = sg.stage([&](Stager::Pass &p) {
+    p.in(head, 3 * c, &d_head); p.in(tail, 3 * c, &d_tail);
+    if (wps_start) p.in(wps_start, nwp, &d_wp0);
+    p.in(T, N, &d_T); p.in(hpolys, nhp, &d_hp);
+    p.out(nxi, &d_xi); p.rows(3 * nxi, &d_verts);
+    // count | overlap status | residual: one row per waypoint each
+    p.rows(N - 1, &count); p.rows(N - 1, &ostat); p.out(N - 1, &d_res);
+    p.out(nwp, &d_wps); p.out(nco, &d_co); p.rows(1, &d_cost); p.doubles(wmax, &d_work);
+    R = anet::lbfgs_result_rows(p.c, ld);
+    // anet_polytope_vertices_dev keeps its (N - 1) batch depths at the head of the context's scratch, which is the stager's staging
+    // area: every upload has left it in stream order by the time the enumeration runs, and it must be large enough to hold them
+    p.at_least(N - 1);
+  });
   if (rc) return rc;
-  double *d_head, *d_tail, *d_wp0 = nullptr, *d_T, *d_hp;
-  if ((rc = sg.upload(head, 3 * c, &d_head))) return rc;
-  if ((rc = sg.upload(tail, 3 * c, &d_tail))) return rc;
-  if (wps_start && (rc = sg.upload(wps_start, nwp, &d_wp0))) return rc;
-  if ((rc = sg.upload(T, N, &d_T))) return rc;
-  if ((rc = sg.upload(hpolys, nhp, &d_hp))) return rc;
-  double *d_xi = sg.reserve(nxi), *d_verts = sg.reserve(3 * nxi);
-  // count | overlap status | residual: one row of ld per waypoint each (the int32 rows take the front half of theirs)
-  double *d_cnt = sg.reserve(N - 1), *d_ost = sg.reserve(N - 1), *d_res = sg.reserve(N - 1);
-  double *d_wps = sg.reserve(nwp), *d_co = sg.reserve(nco), *d_cost = sg.reserve(1), *d_work = sg.reserve(wrows);
-  const anet::LbfgsResultRows R = anet::lbfgs_result_rows(sg.reserve(irows), sg.ld);
-  int32_t *count = (int32_t *)d_cnt, *ostat = (int32_t *)d_ost;
   hipStream_t st = ctx->stream;
-  const int64_t ld = sg.ld;
-  // anet_polytope_vertices_dev keeps its (N - 1) batch depths at the head of the context's scratch, which is the stager's staging
-  // area of batch * mx doubles: every upload has left it in stream order by now, and it must be large enough to hold them
-  if ((int64_t)(N - 1) * batch > batch * mx) return fail(ctx, ANET_ERR_INVALID, "anet_lbfgs_minco_sfc: staging area smaller than the depths");
   if ((rc = anet_sfc_overlap_vertices_dev(ctx, N, batch, ld, M, d_hp, epsilon, K, d_verts, count, ostat, d_work, st))) return rc;
   if (d_wp0) {
     if ((rc = anet_sfc_backward_p_dev(ctx, N, batch, ld, K, d_verts, count, d_wp0, d_xi, d_res, d_work, st))) return rc;
@@ -270,10 +262,7 @@ int anet_lbfgs_minco_sfc(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batc
                                 opt_flags, max_evals, min_duration, w_norm, d_work, d_cost, d_wps, coeffs_out ? d_co : nullptr,
                                 R.status, R.iters, R.evals, st);
   if (rc) return rc;
-  if (status) ANET_HIP(ctx, hipMemcpyAsync(status, R.status, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, st));
-  if (iters) ANET_HIP(ctx, hipMemcpyAsync(iters, R.iters, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, st));
-  if (evals) ANET_HIP(ctx, hipMemcpyAsync(evals, R.evals, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, st));
-  if (cost) ANET_HIP(ctx, hipMemcpyAsync(cost, d_cost, sizeof(double) * batch, hipMemcpyDeviceToHost, st));
+  if ((rc = download_results(ctx, batch, R, d_cost, status, iters, evals, cost, st))) return rc;
   if (overlap_status) {  // [(N-1)][ld] on the device -> [batch][N-1]
     std::vector<int32_t> h((size_t)(N - 1) * ld);
     for (int w = 0; w < N - 1; ++w)

@@ -152,17 +152,14 @@ int anet_minco_solve(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batch, c
   if (!head || !tail || !T || (n_pieces > 1 && !wps))
     return fail(ctx, ANET_ERR_INVALID, "anet_minco_solve: NULL input");
   const int N = n_pieces;
-  const int64_t n_in = 6 * (int64_t)c + (int64_t)(N - 1) * 3 + N;
   const int64_t n_co = (int64_t)N * 3 * 2 * s;
-  Stager st;
-  rc = make_stager(ctx, batch, n_in > n_co ? n_in : n_co, n_in + n_co + 1, &st);
+  Stager st(ctx, batch);
+  double *d_head, *d_tail, *d_wps, *d_T, *d_co, *d_en;
+  rc = st.stage([&](Stager::Pass &p) {
+    p.in(head, 3 * c, &d_head); p.in(tail, 3 * c, &d_tail); p.in(wps, (int64_t)(N - 1) * 3, &d_wps); p.in(T, N, &d_T);
+    p.out(n_co, &d_co); p.rows(1, &d_en);
+  });
   if (rc) return rc;
-  double *d_head, *d_tail, *d_wps, *d_T;
-  if ((rc = st.upload(head, 3 * c, &d_head))) return rc;
-  if ((rc = st.upload(tail, 3 * c, &d_tail))) return rc;
-  if ((rc = st.upload(wps, (int64_t)(N - 1) * 3, &d_wps))) return rc;
-  if ((rc = st.upload(T, N, &d_T))) return rc;
-  double *d_co = st.reserve(n_co), *d_en = st.reserve(1);
   rc = anet_minco_solve_dev(ctx, s, c, N, batch, st.ld, d_head, d_tail, d_wps, d_T, coeffs ? d_co : nullptr, d_en,
                             ctx->stream);
   if (rc) return rc;
@@ -200,20 +197,15 @@ int anet_minco_sample_costs(anet_ctx *ctx, int s, int c, int n_pieces, int64_t s
   if (samples == 0) return ANET_OK;
   if (!head || !tail || !T || !cost || (n_pieces > 1 && !wps)) return fail(ctx, ANET_ERR_INVALID, "anet_minco_sample_costs: NULL pointer");
   const int N = n_pieces;
-  const int64_t npb = 6 * (int64_t)c + 3 * (int64_t)(N - 1);   // the one problem: head, tail, waypoints (ldp = 1)
-  Stager st;
-  rc = make_stager(ctx, samples, N, N + 1 + (npb + samples - 1) / samples + 1, &st);
+  // (the one problem -- head, tail, waypoints -- is shared by every sample: ldp = 1)
+  Stager st(ctx, samples);
+  double *d_T, *d_cost, *d_head, *d_tail, *d_wps;
+  rc = st.stage([&](Stager::Pass &p) {
+    p.in(T, N, &d_T); p.rows(1, &d_cost);
+    p.shared(head, 3 * c, &d_head); p.shared(tail, 3 * c, &d_tail); p.shared(wps, 3 * (int64_t)(N - 1), &d_wps);
+  });
   if (rc) return rc;
-  double *d_T;
-  if ((rc = st.upload(T, N, &d_T))) return rc;
-  if ((rc = st.flush())) return rc;
-  double *d_cost = st.reserve(1);
-  double *d_prob = st.reserve((npb + samples - 1) / samples + 1);
-  ANET_HIP(ctx, hipMemcpyAsync(d_prob, head, sizeof(double) * 3 * c, hipMemcpyHostToDevice, ctx->stream));
-  ANET_HIP(ctx, hipMemcpyAsync(d_prob + 3 * c, tail, sizeof(double) * 3 * c, hipMemcpyHostToDevice, ctx->stream));
-  if (N > 1) ANET_HIP(ctx, hipMemcpyAsync(d_prob + 6 * c, wps, sizeof(double) * 3 * (N - 1), hipMemcpyHostToDevice, ctx->stream));
-  rc = anet_minco_sample_costs_dev(ctx, s, c, N, 1, samples, st.ld, 1, d_prob, d_prob + 3 * c, d_prob + 6 * c, d_T, rho, d_cost,
-                                   ctx->stream);
+  rc = anet_minco_sample_costs_dev(ctx, s, c, N, 1, samples, st.ld, 1, d_head, d_tail, d_wps, d_T, rho, d_cost, ctx->stream);
   if (rc) return rc;
   ANET_HIP(ctx, hipMemcpyAsync(cost, d_cost, sizeof(double) * samples, hipMemcpyDeviceToHost, ctx->stream));
   ANET_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -228,15 +220,10 @@ int anet_traj_eval(anet_ctx *ctx, int s, int n_pieces, int64_t batch, const doub
   if (batch == 0 || nq <= 0) return nq < 0 ? fail(ctx, ANET_ERR_INVALID, "nq < 0") : ANET_OK;
   if (!coeffs || !T || !tq || !out) return fail(ctx, ANET_ERR_INVALID, "anet_traj_eval: NULL pointer");
   const int64_t nco = (int64_t)n_pieces * 3 * 2 * s;
-  const int64_t mx = nco > 3 * (int64_t)nq ? nco : 3 * (int64_t)nq;
-  Stager st;
-  rc = make_stager(ctx, batch, mx, nco + n_pieces + nq + 3 * (int64_t)nq, &st);
+  Stager st(ctx, batch);
+  double *d_co, *d_T, *d_tq, *d_out;
+  rc = st.stage([&](Stager::Pass &p) { p.in(coeffs, nco, &d_co); p.in(T, n_pieces, &d_T); p.in(tq, nq, &d_tq); p.out(3 * (int64_t)nq, &d_out); });
   if (rc) return rc;
-  double *d_co, *d_T, *d_tq;
-  if ((rc = st.upload(coeffs, nco, &d_co))) return rc;
-  if ((rc = st.upload(T, n_pieces, &d_T))) return rc;
-  if ((rc = st.upload(tq, nq, &d_tq))) return rc;
-  double *d_out = st.reserve(3 * (int64_t)nq);
   rc = anet_traj_eval_dev(ctx, s, n_pieces, batch, st.ld, d_co, d_T, nq, d_tq, deriv, d_out, ctx->stream);
   if (rc) return rc;
   return st.download(d_out, 3 * (int64_t)nq, out);
@@ -250,13 +237,10 @@ int anet_traj_cost(anet_ctx *ctx, int s, int n_pieces, int64_t batch, const doub
   if (batch == 0) return ANET_OK;
   if (!coeffs || !T || !cost) return fail(ctx, ANET_ERR_INVALID, "anet_traj_cost: NULL pointer");
   const int64_t nco = (int64_t)n_pieces * 3 * 2 * s;
-  Stager st;
-  rc = make_stager(ctx, batch, nco, nco + n_pieces + 1, &st);
+  Stager st(ctx, batch);
+  double *d_co, *d_T, *d_cost;
+  rc = st.stage([&](Stager::Pass &p) { p.in(coeffs, nco, &d_co); p.in(T, n_pieces, &d_T); p.rows(1, &d_cost); });
   if (rc) return rc;
-  double *d_co, *d_T;
-  if ((rc = st.upload(coeffs, nco, &d_co))) return rc;
-  if ((rc = st.upload(T, n_pieces, &d_T))) return rc;
-  double *d_cost = st.reserve(1);
   rc = anet_traj_cost_dev(ctx, s, n_pieces, batch, st.ld, d_co, d_T, m34, d_cost, ctx->stream);
   if (rc) return rc;
   ANET_HIP(ctx, hipMemcpyAsync(cost, d_cost, sizeof(double) * batch, hipMemcpyDeviceToHost, ctx->stream));
@@ -321,13 +305,10 @@ int anet_traj_cost_grad_T(anet_ctx *ctx, int s, int n_pieces, int64_t batch, con
   if (batch == 0) return ANET_OK;
   if (!coeffs || !T || !gradT) return fail(ctx, ANET_ERR_INVALID, "anet_traj_cost_grad_T: NULL pointer");
   const int64_t nco = (int64_t)n_pieces * 3 * 2 * s;
-  Stager st;
-  rc = make_stager(ctx, batch, nco, nco + 2 * (int64_t)n_pieces, &st);
+  Stager st(ctx, batch);
+  double *d_co, *d_T, *d_g;
+  rc = st.stage([&](Stager::Pass &p) { p.in(coeffs, nco, &d_co); p.in(T, n_pieces, &d_T); p.out(n_pieces, &d_g); });
   if (rc) return rc;
-  double *d_co, *d_T;
-  if ((rc = st.upload(coeffs, nco, &d_co))) return rc;
-  if ((rc = st.upload(T, n_pieces, &d_T))) return rc;
-  double *d_g = st.reserve(n_pieces);
   rc = anet_traj_cost_grad_T_dev(ctx, s, n_pieces, batch, st.ld, d_co, d_T, m34, d_g, ctx->stream);
   if (rc) return rc;
   return st.download(d_g, n_pieces, gradT);
@@ -357,13 +338,10 @@ int anet_traj_max_rate(anet_ctx *ctx, int s, int n_pieces, int64_t batch, const 
   if (batch == 0) return ANET_OK;
   if (!coeffs || !T || !rate) return fail(ctx, ANET_ERR_INVALID, "anet_traj_max_rate: NULL pointer");
   const int64_t nco = (int64_t)n_pieces * 3 * 2 * s;
-  Stager st;
-  rc = make_stager(ctx, batch, nco, nco + 2 * (int64_t)n_pieces, &st);
+  Stager st(ctx, batch);
+  double *d_co, *d_T, *d_r;
+  rc = st.stage([&](Stager::Pass &p) { p.in(coeffs, nco, &d_co); p.in(T, n_pieces, &d_T); p.out(n_pieces, &d_r); });
   if (rc) return rc;
-  double *d_co, *d_T;
-  if ((rc = st.upload(coeffs, nco, &d_co))) return rc;
-  if ((rc = st.upload(T, n_pieces, &d_T))) return rc;
-  double *d_r = st.reserve(n_pieces);
   rc = anet_traj_max_rate_dev(ctx, s, n_pieces, batch, st.ld, d_co, d_T, which, d_r, ctx->stream);
   if (rc) return rc;
   return st.download(d_r, n_pieces, rate);

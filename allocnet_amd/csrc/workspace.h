@@ -1,7 +1,7 @@
 // The shape of every device workspace of the library, each written ONCE: a function runs a bump cursor over the regions in order
 // and returns typed pointers plus the total.  The anet_*_workspace() functions call it on a null base (measure only), the
-// *_dev_impls on the buffer; the host entry points shape their staging buffers with the same cursor (api_internal.h,
-// stage_scratch).  Host C++17 only, no HIP include, no device code: tests/cpp/test_workspace_layout.cpp carves every layout in
+// *_dev_impls on the buffer.  The host entry points shape their buffers with the same cursor: the trajectory-major ones that
+// transpose state theirs in staging.h's terms (Stager::stage), the contiguous ones in api_internal.h's stage_scratch.  Host C++17 only, no HIP include, no device code: tests/cpp/test_workspace_layout.cpp carves every layout in
 // host memory under a sanitizer.  DESIGN.md section 8i.
 #pragma once
 #include <stddef.h>
@@ -166,11 +166,12 @@ inline LbfgsLayout sfc_backward_p_ws(double *w, int N, int K, int64_t ld) {
 
 // status | iterations | evaluations of an L-BFGS run (k_lbfgs_results), int32 rows of ld
 struct LbfgsResultRows { int32_t *status, *iters, *evals; int64_t doubles; };
-inline LbfgsResultRows lbfgs_result_rows(double *w, int64_t ld) {
-  Cursor c(w);
+inline LbfgsResultRows lbfgs_result_rows(Cursor &c, int64_t ld) {
+  const int64_t at = c.doubles();
   LbfgsResultRows R{c.take<int32_t>(ld), c.take<int32_t>(ld), c.take<int32_t>(ld), 0};
-  R.doubles = c.doubles();
+  R.doubles = c.doubles() - at;
   return R;
 }
+inline LbfgsResultRows lbfgs_result_rows(double *w, int64_t ld) { Cursor c(w); return lbfgs_result_rows(c, ld); }
 
 }  // namespace anet
