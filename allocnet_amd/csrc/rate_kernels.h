@@ -7,6 +7,12 @@
 // interval exactly) and refined by bisection.  Same candidates {0, roots, 1}, same maximum.
 // checkMaxVelRate/checkMaxAccRate (:275-314, "no root of ||.||^2 - max^2 in (0,1) and both ends below")
 // is that maximum compared with the bound.
+// q and its derivative dq only LOCATE the candidates.  Their values are taken from the component polynomials,
+// ||u(tau)||^2 with one Horner per axis, as the reference's getVel(tau * duration).squaredNorm() (:218, :267): the
+// monomial coefficients of q are sums of products of the components' and can be far larger than q itself (a
+// Chebyshev-like velocity of degree 6 has q <= 1 with coefficients of 1e8), so Horner on q loses in relative
+// accuracy the square of what Horner on a component loses -- 2e-8 against 3e-13 on that piece, measured.  An error in a
+// candidate's location enters its value to second order only, so dq may stay in the monomial basis.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -63,14 +69,20 @@ __global__ void __launch_bounds__(64) k_piece_max_rate(RateArgs a) {
     for (int j = 0; j <= MAXM; ++j)
 #pragma unroll
       for (int k = 0; k <= MAXM; ++k) q[j + k] = __builtin_fma(u[ax][j], u[ax][k], q[j + k]);
-  auto evalq = [&](double t) {
-    double v = 0.0;
+  // the value of a candidate: ||u(t)||^2 from the three components, never from q (see the header)
+  auto evalr = [&](double t) {
+    double r = 0.0;
 #pragma unroll
-    for (int k = 2 * MAXM; k >= 0; --k) v = __builtin_fma(v, t, q[k]);
-    return v;
+    for (int ax = 0; ax < 3; ++ax) {
+      double v = 0.0;
+#pragma unroll
+      for (int k = MAXM; k >= 0; --k) v = __builtin_fma(v, t, u[ax][k]);
+      r = __builtin_fma(v, v, r);
+    }
+    return r;
   };
   const int n = 2 * m - 1;  // degree of dq
-  double best = fmax(evalq(0.0), evalq(1.0));
+  double best = fmax(evalr(0.0), evalr(1.0));
   double dq[MAXN + 1];
   double nrm = 0.0;
 #pragma unroll
@@ -80,7 +92,7 @@ __global__ void __launch_bounds__(64) k_piece_max_rate(RateArgs a) {
   }
   double result;
   if (nrm < 2.220446049250313e-16 || n < 1) {  // DBL_EPSILON: constant rate (trajectory.hpp:189-192)
-    result = evalq(0.0);
+    result = evalr(0.0);
   } else {
     // Bernstein coefficients of dq on [0,1], degree n: bz[i] = sum_{k<=i} C(i,k)/C(n,k) dq[k]
     double stk[24][MAXN + 1];  // subdivision stack (private memory)
@@ -131,11 +143,11 @@ __global__ void __launch_bounds__(64) k_piece_max_rate(RateArgs a) {
           const int sm = (fm > 0.0) - (fm < 0.0);
           if (sm == first) l = mid; else h = mid;
         }
-        best = fmax(best, evalq(0.5 * (l + h)));
+        best = fmax(best, evalr(0.5 * (l + h)));
         continue;
       }
       if (hi - lo < 1e-13 || sp >= 22) {  // unresolvable cluster of roots: its location is known well enough
-        best = fmax(best, evalq(0.5 * (lo + hi)));
+        best = fmax(best, evalr(0.5 * (lo + hi)));
         continue;
       }
       // de Casteljau split at the midpoint: left = diagonal, right = last row

@@ -217,6 +217,9 @@ double oracle_traj_cost(int order, int N, const double *coeffs, const double *T,
                               {20160 * t5, 10800 * t4, 4800 * t3, m34 * t2},
                               {5040 * t4, 2880 * t3, m34 * t2, 576 * t}};
       memcpy(Q, q, sizeof(q));
+    } else if (order == 2) {
+      const double q[4][4] = {{12 * t3, 6 * t2, 0, 0}, {6 * t2, 4 * t, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+      memcpy(Q, q, sizeof(q));
     } else {
       const double q[4][4] = {{720 * t5, 360 * t4, 120 * t3, 0}, {360 * t4, 192 * t3, 72 * t2, 0},
                               {120 * t3, 72 * t2, 36 * t, 0}, {0, 0, 0, 0}};

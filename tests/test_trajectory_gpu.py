@@ -1,11 +1,15 @@
 """GPU parity: Trajectory/Piece evaluation and getTrajCost vs the reference-generated fixtures
-(network/utils/trajectory.py outputs) and the C/numpy oracle."""
+(network/utils/trajectory.py outputs) and the C/numpy oracle; and vs the exact-arithmetic references of
+tests/golden/max_rate_cases.npz (keys tr{s}{N}_*) at the a-priori float64 bounds of tests/trajectory_mp."""
+import os
+
 import numpy as np
 import pytest
 
 from oracle import minco_np as onp
 from oracle import cbind
-from tests.util import golden_files, random_problem, rel_err
+from tests import trajectory_mp as tmp
+from tests.util import GOLDEN, golden_files, random_problem, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -52,9 +56,8 @@ def test_eval_batched_vs_oracle(anet_ctx, s, N):
     for m34 in (1400.0, 1440.0):
         got = aa.traj_cost(coeffs, T, s, m34, ctx=anet_ctx)
         for b in range(0, B, 7):
-            if s > 2:
-                assert abs(got[b] - onp.traj_cost(coeffs[b], T[b], s, m34)) <= 1e-11 * abs(got[b])
-                assert abs(got[b] - cbind.traj_cost(s, coeffs[b], T[b], m34)) <= 1e-11 * abs(got[b])
+            assert abs(got[b] - onp.traj_cost(coeffs[b], T[b], s, m34)) <= 1e-11 * abs(got[b])
+            assert abs(got[b] - cbind.traj_cost(s, coeffs[b], T[b], m34)) <= 1e-11 * abs(got[b])
 
 
 @pytest.mark.parametrize("s", [2, 3, 4])
@@ -115,3 +118,60 @@ def test_time_gradient_matches_reference_autograd(anet_ctx, path):
     g = aa.traj_cost_grad_T(z, d["T"][None], m34=1400.0, ctx=anet_ctx)[0]
     ref = d["dcost_dT"]
     assert np.abs(g - ref).max() <= 1e-10 * max(1.0, np.abs(ref).max())
+
+
+@pytest.fixture(scope="module")
+def traj_fx():
+    return np.load(os.path.join(GOLDEN, "max_rate_cases.npz"))
+
+
+def _tiled(traj_fx, s, N, B):
+    """the fixture's trajectories of (s, N) tiled over B lanes with a stride coprime to their number"""
+    p = "tr%d%d_" % (s, N)
+    n = len(traj_fx[p + "T"])
+    src = (np.arange(B) * 3) % n
+    assert n % 3 != 0 and set(src) == set(range(n))
+    return p, src, traj_fx[p + "coeffs"][src].copy(), traj_fx[p + "T"][src].copy()
+
+
+@pytest.mark.parametrize("N", [3, 1])
+@pytest.mark.parametrize("s", [2, 3, 4])
+def test_eval_matches_exact_reference(anet_ctx, traj_fx, s, N):
+    """k_traj_eval, one full 256-lane block and a 44-lane tail, durations {0.05, 1, 20} in every order: derivatives 0..3
+    at 0, at both knots exactly, at the end, beyond the end and inside every piece, every lane, per axis within
+    16 eps sum_k |w_k c_k t^k| of the exact polynomial (trajectory_mp.eval_bound)."""
+    import allocnet_amd as aa
+    B = 300
+    p, src, coeffs, T = _tiled(traj_fx, s, N, B)
+    tq = traj_fx[p + "tq"][src].copy()
+    n, nq = len(traj_fx[p + "T"]), tq.shape[1]
+    for d in range(4):
+        bound = np.array([[tmp.eval_bound(traj_fx[p + "coeffs"][j], traj_fx[p + "T"][j], traj_fx[p + "tq"][j, q], d)
+                           for q in range(nq)] for j in range(n)])
+        got = aa.traj_eval(coeffs, T, tq, d, ctx=anet_ctx)
+        err = np.abs(got - traj_fx[p + "ev"][src, d])
+        print("s=%d N=%d d=%d worst |err| / bound: %.4f" % (s, N, d, (err / np.maximum(bound[src], 1e-300)).max()))
+        assert (err <= bound[src]).all(), (d, np.argwhere(err > bound[src])[:8])
+
+
+@pytest.mark.parametrize("N", [3, 1])
+@pytest.mark.parametrize("s", [2, 3, 4])
+def test_cost_and_time_gradient_match_exact_reference(anet_ctx, traj_fx, s, N):
+    """k_traj_cost and its gradT output for m34 in (1400, 1440), every lane and every piece, against the exactly
+    integrated 1/2 int ||p^(s)||^2 (plus the m34 term) and its exact derivative in each duration, within
+    32 eps sum |z_j| |Q_jk| |z_k| (trajectory_mp.cost_bound / cost_grad_bound)."""
+    import allocnet_amd as aa
+    B = 300
+    p, src, coeffs, T = _tiled(traj_fx, s, N, B)
+    n = len(traj_fx[p + "T"])
+    for k, m34 in enumerate((1400.0, 1440.0)):
+        cb = np.array([tmp.cost_bound(traj_fx[p + "coeffs"][j], traj_fx[p + "T"][j], s, m34) for j in range(n)])
+        gb = np.array([tmp.cost_grad_bound(traj_fx[p + "coeffs"][j], traj_fx[p + "T"][j], s, m34) for j in range(n)])
+        cost = aa.traj_cost(coeffs, T, s, m34, ctx=anet_ctx)
+        grad = aa.traj_cost_grad_T(coeffs, T, m34=m34, ctx=anet_ctx)
+        ce = np.abs(cost - traj_fx[p + "cost"][k, src])
+        ge = np.abs(grad - traj_fx[p + "gradT"][k, src])
+        print("s=%d N=%d m34=%g worst |err| / bound: cost %.4f gradT %.4f" % (s, N, m34, (ce / cb[src]).max(),
+                                                                            (ge / gb[src]).max()))
+        assert (ce <= cb[src]).all(), np.argwhere(ce > cb[src])[:8]
+        assert (ge <= gb[src]).all(), np.argwhere(ge > gb[src])[:8]
