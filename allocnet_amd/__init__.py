@@ -8,6 +8,7 @@ from .context import Context, default_context  # noqa: F401
 from .minco import MINCO, MINCO_S2NU, MINCO_S3NU, MINCO_S4NU, minco_solve, minco_solve_dev, bind_minco_solve, BoundMincoSolve, recommended_ld, minco_cost_grad, minco_cost_grad_dev, minco_cost_grad_launches, minco_piece_grad_shape, make_penalty, minco_sample_costs, minco_sample_costs_dev  # noqa: F401
 
 from .trajectory import Piece, Trajectory, traj_eval, traj_cost, traj_cost_grad_T, traj_max_rate  # noqa: F401
+from .trajectory import traj_row_margin, traj_qp_margins  # noqa: F401
 from . import lbfgs  # noqa: F401
 from .lbfgs import (lbfgs_parameter_t, lbfgs_strerror, lbfgs_mvie, lbfgs_minco, lbfgs_minco_dev,  # noqa: F401
                     launch_order_from_counts, lbfgs_optimize_dev, lbfgs_optimize)

@@ -46,6 +46,9 @@ PROTOTYPES = {
     "anet_traj_max_rate_dev": (c_int, [c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int,
                                        c_void_p, c_void_p]),
     "anet_traj_max_rate": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p]),
+    "anet_traj_row_margin_dev": (c_int, [c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int, c_int] +
+                                 [c_void_p] * 5),
+    "anet_traj_row_margin": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 4),
     "anet_traj_cost_dev": (c_int, [c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p,
                                    c_double, c_void_p, c_void_p]),
     "anet_traj_cost": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_double, c_void_p]),

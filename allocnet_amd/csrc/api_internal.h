@@ -15,6 +15,7 @@
 //   api_timenet.hip    the time-allocation network: weights handle, batched inference
 //   api_polytope.hip   vertex enumeration of polytopes (geo_utils::enumerateVs)
 //   api_sfc.hip        waypoints as vertex weights of corridor overlaps: the transform, its inverse, the constrained MINCO L-BFGS
+//   api_margin.hip     exact margins of trajectories against corridor and box-limit rows
 //   piece_grad_unit.hip, qp_ipm_fuse_unit.hip: kernels scheduled for ILP, reached through launch functions
 // Only what two or more units use is here.  Nothing here is exported: the library's dynamic symbols stay the anet_* entry
 // points (and the kernels).

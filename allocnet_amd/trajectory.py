@@ -70,6 +70,58 @@ def traj_max_rate(coeffs, T, which, ctx=None):
     return out
 
 
+def traj_row_margin(coeffs, T, rows, deriv=0, ctx=None):
+    """Exact per-piece margin against linear rows a.x <= b (anet_traj_row_margin): the maximum over the non-padding rows of a
+    piece and over t in [0, T_i] of a . p^(deriv)(t) - b.  Positive: the deepest excursion; negative: the clearance kept; -inf:
+    no row; NaN: a non-finite input of that piece.  coeffs (B,N,3,D), T (B,N), rows (B,N,M,4) with all-zero rows as padding ->
+    (margin (B,N), row (B,N) int32: a maximising row or -1, t (B,N): its local time)."""
+    ctx = ctx or default_context()
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+    T = np.ascontiguousarray(T, dtype=np.float64)
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    B, N, three, D = coeffs.shape
+    if three != 3 or T.shape != (B, N) or rows.ndim != 4 or rows.shape[:2] != (B, N) or rows.shape[3] != 4:
+        raise ValueError("shape mismatch")
+    M = rows.shape[2]
+    margin = np.empty((B, N))
+    row = np.empty((B, N), dtype=np.int32)
+    t = np.empty((B, N))
+    ctx.check(ctx.lib.anet_traj_row_margin(ctx.handle, D // 2, N, B, _ptr(coeffs), _ptr(T), int(deriv), M, _ptr(rows),
+                                           _ptr(margin), _ptr(row), _ptr(t)))
+    return margin, row, t
+
+
+def box_rows(limit):
+    """The six rows +-e_axis . x <= limit of the per-axis boxes of QPSolver::solve (qp_solver.hpp:268-296), (6, 4)."""
+    r = np.zeros((6, 4))
+    for ax in range(3):
+        r[2 * ax, ax] = 1.0
+        r[2 * ax + 1, ax] = -1.0
+    r[:, 3] = float(limit)
+    return r
+
+
+def traj_qp_margins(coeffs, T, hpolys, max_vel, max_acc, ctx=None):
+    """The exact margins of the three inequality groups QPSolver::solve samples: corridor rows on the position, +-v_axis <=
+    max_vel, +-a_axis <= max_acc.  hpolys (B,N,M,4) -> (corridor, vel_box, acc_box), each (B,N)."""
+    coeffs = np.asarray(coeffs, dtype=np.float64)
+    B, N = coeffs.shape[:2]
+    corridor = traj_row_margin(coeffs, T, hpolys, 0, ctx=ctx)[0]
+    vel = traj_row_margin(coeffs, T, np.broadcast_to(box_rows(max_vel), (B, N, 6, 4)), 1, ctx=ctx)[0]
+    acc = traj_row_margin(coeffs, T, np.broadcast_to(box_rows(max_acc), (B, N, 6, 4)), 2, ctx=ctx)[0]
+    return corridor, vel, acc
+
+
+def _stack_hpolys(hPolys):
+    """A list of (M_i, 4) polytopes -> (1, N, max M_i, 4), padded with zero rows."""
+    hp = [np.asarray(h, dtype=np.float64).reshape(-1, 4) for h in hPolys]
+    M = max(1, max(h.shape[0] for h in hp))
+    out = np.zeros((1, len(hp), M, 4))
+    for i, h in enumerate(hp):
+        out[0, i, :h.shape[0]] = h
+    return out
+
+
 def piece_normalized_coeffs(coeffs, T, deriv, ctx=None):
     """Piece::normalizePosCoeffMat / normalizeVelCoeffMat / normalizeAccCoeffMat (trajectory.hpp:135-171) for a batch of pieces:
     coefficients of position (deriv 0), velocity (1) or acceleration (2) in normalised time.  coeffs (P,3,D), T (P,) -> (P,3,D-deriv)."""
@@ -143,6 +195,11 @@ class Piece:
 
     def checkMaxAccRate(self, maxAccRate):
         return self.getMaxAccRate() < maxAccRate
+
+    def getCorridorMargin(self, hPoly):
+        """Exact max over the rows a.x <= b of hPoly (M, 4) and over the piece of a . p(t) - b (no counterpart in the reference)."""
+        return float(traj_row_margin(self.coeffMat[None, None], np.array([[self.duration]]), _stack_hpolys([hPoly]), 0,
+                                     ctx=self._ctx)[0][0, 0])
 
 
 class Trajectory:
@@ -229,6 +286,27 @@ class Trajectory:
 
     def checkMaxAccRate(self, maxAccRate):
         return self.getMaxAccRate() < maxAccRate
+
+    # --- exact margins against the corridor and the per-axis boxes (no counterpart in the reference, which samples them)
+    def getCorridorMargin(self, hPolys, per_piece=False):
+        """Maximum over the pieces of the exact corridor margin, piece i against hPolys[i] (rows a.x <= b); per_piece=True: the
+        triple (margin, row, t) of arrays over the pieces."""
+        co, T = self._arrays()
+        if len(hPolys) != len(self.pieces):
+            raise ValueError("one polytope per piece")
+        m, r, t = traj_row_margin(co, T, _stack_hpolys(hPolys), 0, ctx=self._ctx)
+        return (m[0], r[0], t[0]) if per_piece else float(m.max())
+
+    def checkCorridor(self, hPolys, tol=0.0):
+        return self.getCorridorMargin(hPolys) <= tol
+
+    def checkBoxLimits(self, max_vel, max_acc):
+        """True when every axis of the velocity stays within +-max_vel and of the acceleration within +-max_acc, exactly."""
+        co, T = self._arrays()
+        shape = (1, len(self.pieces), 6, 4)
+        vel = traj_row_margin(co, T, np.broadcast_to(box_rows(max_vel), shape), 1, ctx=self._ctx)[0]
+        acc = traj_row_margin(co, T, np.broadcast_to(box_rows(max_acc), shape), 2, ctx=self._ctx)[0]
+        return bool(vel.max() <= 0.0 and acc.max() <= 0.0)
 
     # --- the vehicle's own terms: thrust, attitude, body rate through the flatness map (flatness.py) ---------------
     def getFlatState(self, t, flatmap):

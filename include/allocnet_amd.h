@@ -200,6 +200,22 @@ int anet_traj_max_rate_dev(anet_ctx *ctx, int s, int n_pieces, int64_t batch, in
 int anet_traj_max_rate(anet_ctx *ctx, int s, int n_pieces, int64_t batch, const double *coeffs,
                        const double *T, int which, double *rate);
 
+/* Exact margin of every piece against linear rows a.x <= b (no counterpart in the reference, whose solvers hold these rows at
+ * sample points only): for deriv d in {0, 1, 2}
+ *     margin[i] = max over the non-padding rows r of piece i, max over t in [0, T_i], of  a_r . p_i^(d)(t) - b_r
+ * positive: the deepest excursion out of the polytope; negative: the clearance kept; -inf: the piece has no row; NaN: a NaN or
+ * infinite coefficient, duration or row field of that piece.  With d = 0 and corridor rows this is the corridor margin; with
+ * d = 1, 2 and the six rows +-e_axis, b = MaxVelBox / MaxAccBox it is the margin of the box rows of QPSolver::solve
+ * (planner/qp_solver.hpp:244-296).  rows: [N*M*4][ld] in the layout of `hpolys` below (dev) / [batch][N][M][4] (host), all-zero
+ * rows are padding, 1 <= M = poly_rows <= ANET_MAX_POLY_ROWS.  margin, t: double [N][ld] (dev) / [batch][N] (host); row: int32, the
+ * same shapes.  row (a maximising row, -1 without one) and t (its local time in [0, T_i], 0 without one) may be NULL; they are
+ * diagnostics: a_row . p^(d)(t) - b_row reproduces margin.  Accuracy: 32 eps (sum_ax |a_ax| sum_k |u_ax,k| + |b|), u the
+ * coefficients of p^(d) in normalised time (csrc/corridor_margin_kernels.h). */
+int anet_traj_row_margin_dev(anet_ctx *ctx, int s, int n_pieces, int64_t batch, int64_t ld, const double *coeffs, const double *T,
+                             int deriv, int poly_rows, const double *rows, double *margin, int32_t *row, double *t, void *stream);
+int anet_traj_row_margin(anet_ctx *ctx, int s, int n_pieces, int64_t batch, const double *coeffs, const double *T, int deriv,
+                         int poly_rows, const double *rows, double *margin, int32_t *row, double *t);
+
 /* Replaces Piece<D>::normalizePosCoeffMat / normalizeVelCoeffMat / normalizeAccCoeffMat (gcopter/trajectory.hpp:135-171) for a
  * batch of independent pieces: the coefficients of the position (deriv = 0), velocity (1) or acceleration (2) polynomial of each
  * piece in normalised time tau = t / duration, highest power first: column i = (falling factorial of its power) * coeffMat.col(i) *

@@ -8,6 +8,8 @@
 // anet::Vec3 / anet::Matrix which convert to and from Eigen types by duck typing (core.hpp).
 // getMax{Vel,Acc}Rate / checkMax{Vel,Acc}Rate (trajectory.hpp:177-314, 576-630) are provided through
 // anet_traj_max_rate (Bernstein-subdivision root isolation instead of Sturm sequences, same extrema).
+// getCorridorMargin / checkCorridor have no counterpart in the reference: the exact maximum over a piece of a.p(t) - b over the rows
+// a.x <= b of its corridor polytope (anet_traj_row_margin), which the reference's solvers hold at sample points only.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -83,6 +85,23 @@ class Piece {
   inline double getMaxAccRate() const { return maxRate(2); }
   inline bool checkMaxVelRate(const double &maxVelRate) const { return getMaxVelRate() < maxVelRate; }
   inline bool checkMaxAccRate(const double &maxAccRate) const { return getMaxAccRate() < maxAccRate; }
+
+  // exact max over the M rows a.x <= b (row-major M x 4, all-zero rows are padding) and over the piece of a . p(t) - b
+  inline double getCorridorMargin(const double *rows, int M) const {
+    double m = 0.0;
+    anet::Context &ctx = anet::Context::thread_default();
+    ctx.check(anet_traj_row_margin(ctx.get(), (D + 1) / 2, 1, 1, coeffMat.data(), &duration, 0, M, rows, &m, nullptr, nullptr));
+    return m;
+  }
+  // hPoly: any M x 4 matrix with rows() and operator()(r, c), e.g. Eigen::MatrixX4d
+  template <class HPoly>
+  inline double getCorridorMargin(const HPoly &hPoly) const {
+    const int M = (int)hPoly.rows();
+    std::vector<double> rows((size_t)std::max(M, 1) * 4, 0.0);
+    for (int r = 0; r < M; ++r)
+      for (int c = 0; c < 4; ++c) rows[(size_t)r * 4 + c] = hPoly(r, c);
+    return getCorridorMargin(rows.data(), std::max(M, 1));
+  }
 };
 
 template <int D>
@@ -207,6 +226,38 @@ class Trajectory {
   inline double getMaxAccRate() const { return maxRate(2); }
   inline bool checkMaxVelRate(const double &maxVelRate) const { return getMaxVelRate() < maxVelRate; }
   inline bool checkMaxAccRate(const double &maxAccRate) const { return getMaxAccRate() < maxAccRate; }
+
+  // Exact corridor margin, piece i against the rows a.x <= b of polytope i: rows is [N][M][4] row-major with all-zero rows as
+  // padding.  Returns the maximum over the pieces; per_piece (may be null) receives the N margins.
+  inline double getCorridorMargin(const double *rows, int M, double *per_piece = nullptr) const {
+    std::vector<double> co, T;
+    flatten(co, T);
+    std::vector<double> m(T.size());
+    anet::Context &ctx = anet::Context::thread_default();
+    ctx.check(anet_traj_row_margin(ctx.get(), (D + 1) / 2, getPieceNum(), 1, co.data(), T.data(), 0, M, rows, m.data(), nullptr,
+                                   nullptr));
+    double best = m.empty() ? 0.0 : m[0];
+    for (size_t i = 0; i < m.size(); ++i) {
+      best = m[i] > best ? m[i] : best;
+      if (per_piece) per_piece[i] = m[i];
+    }
+    return best;
+  }
+  // hPolys: one M_i x 4 matrix per piece (rows() and operator()(r, c), e.g. std::vector<Eigen::MatrixX4d>)
+  template <class HPoly>
+  inline double getCorridorMargin(const std::vector<HPoly> &hPolys, double *per_piece = nullptr) const {
+    if ((int)hPolys.size() != getPieceNum()) throw anet::Error(ANET_ERR_INVALID, "getCorridorMargin: one polytope per piece");
+    int M = 1;
+    for (const auto &h : hPolys) M = std::max(M, (int)h.rows());
+    std::vector<double> rows(hPolys.size() * (size_t)M * 4, 0.0);
+    for (size_t i = 0; i < hPolys.size(); ++i)
+      for (int r = 0; r < (int)hPolys[i].rows(); ++r)
+        for (int c = 0; c < 4; ++c) rows[(i * M + r) * 4 + c] = hPolys[i](r, c);
+    return getCorridorMargin(rows.data(), M, per_piece);
+  }
+  template <class HPoly>
+  inline bool checkCorridor(const std::vector<HPoly> &hPolys, double tol = 0.0) const { return getCorridorMargin(hPolys) <= tol; }
+  inline bool checkCorridor(const double *rows, int M, double tol = 0.0) const { return getCorridorMargin(rows, M) <= tol; }
 
   // 3 x (N+1) junction positions (trajectory.hpp:440-450), column k = junction k
   inline std::vector<anet::Vec3> getPositions() const {
