@@ -168,8 +168,13 @@ __device__ __forceinline__ void flat_adjoint(const FlatParams &p, const double (
   }
 }
 
-// tilt angle from the quaternion, as process() publishes it
-__device__ __forceinline__ double flat_tilt(const double (&q)[4]) { return acos(1.0 - 2.0 * (q[1] * q[1] + q[2] * q[2])); }
+// Tilt angle from the quaternion: sin^2(tilt / 2) = q1^2 + q2^2, cos^2(tilt / 2) = q0^2 + q3^2.  process() publishes
+// acos(1 - 2 (q1^2 + q2^2)); that form loses a small tilt (1 - 2 x rounds x away: 2 % at 1e-7 rad) and is NaN where x rounds
+// above 1 next to inversion.  The half-angle tangent keeps the relative accuracy of q at every tilt in [0, pi].
+__device__ __forceinline__ double flat_tilt_of(const double s2, const double c2) { return 2.0 * atan2(sqrt(s2), sqrt(c2)); }
+__device__ __forceinline__ double flat_tilt(const double (&q)[4]) {
+  return flat_tilt_of(q[1] * q[1] + q[2] * q[2], q[0] * q[0] + q[3] * q[3]);
+}
 
 // ------------------------------------------------------------------------------------------
 // pointwise: one lane per element
@@ -333,13 +338,13 @@ constexpr int kFlatExtremaRows = 4;
 template <int S>
 __global__ void __launch_bounds__(64 * kFlatExtremaRows) k_traj_flat_extrema(FlatExtremaArgs a) {
   constexpr int D = 2 * S, R = kFlatExtremaRows;
-  __shared__ double red[R][4][64];
+  __shared__ double red[R][5][64];
   const int lane = threadIdx.x, row = threadIdx.y;
   const int64_t b = (int64_t)blockIdx.x * 64 + lane;
   const bool live = b < a.B;
   const int64_t bb = live ? b : a.B - 1;  // (every lane reaches the barrier; lanes past the batch write nothing)
   const int64_t ld = a.ld;
-  double lo = INFINITY, hi = -INFINITY, tilt_cos = 1.0, bdr2 = 0.0;
+  double lo = INFINITY, hi = -INFINITY, tilt_s2 = 0.0, tilt_c2 = INFINITY, bdr2 = 0.0;
   const double inv_res = 1.0 / (double)a.res;
   for (int i = row; i < a.N; i += R) {
     const double Ti = a.T[(int64_t)i * ld + bb];
@@ -352,26 +357,31 @@ __global__ void __launch_bounds__(64 * kFlatExtremaRows) k_traj_flat_extrema(Fla
       flat_forward<false>(a.fp, d[0], d[1], d[2], 0.0, 0.0, m);
       lo = fmin(lo, m.thr);
       hi = fmax(hi, m.thr);
-      tilt_cos = fmin(tilt_cos, 1.0 - 2.0 * (m.q[1] * m.q[1] + m.q[2] * m.q[2]));  // acos decreases: max tilt = acos(min cos)
+      // the tilt grows with sin^2(tilt / 2) and falls with cos^2(tilt / 2): the largest of the one and the smallest of the other
+      // (the same sample up to rounding) give the largest tilt, converted once per trajectory
+      tilt_s2 = fmax(tilt_s2, m.q[1] * m.q[1] + m.q[2] * m.q[2]);
+      tilt_c2 = fmin(tilt_c2, m.q[0] * m.q[0] + m.q[3] * m.q[3]);
       bdr2 = fmax(bdr2, dot3(m.o, m.o));
     }
   }
   red[row][0][lane] = lo;
   red[row][1][lane] = hi;
-  red[row][2][lane] = tilt_cos;
+  red[row][2][lane] = tilt_s2;
   red[row][3][lane] = bdr2;
+  red[row][4][lane] = tilt_c2;
   __syncthreads();
   if (row == 0 && live) {
 #pragma unroll
     for (int r = 1; r < R; ++r) {
       lo = fmin(lo, red[r][0][lane]);
       hi = fmax(hi, red[r][1][lane]);
-      tilt_cos = fmin(tilt_cos, red[r][2][lane]);
+      tilt_s2 = fmax(tilt_s2, red[r][2][lane]);
       bdr2 = fmax(bdr2, red[r][3][lane]);
+      tilt_c2 = fmin(tilt_c2, red[r][4][lane]);
     }
     a.out[b] = lo;
     a.out[ld + b] = hi;
-    a.out[2 * ld + b] = acos(tilt_cos);
+    a.out[2 * ld + b] = flat_tilt_of(tilt_s2, tilt_c2);
     a.out[3 * ld + b] = sqrt(bdr2);
   }
 }

@@ -336,8 +336,8 @@ int anet_flat_backward(anet_ctx *ctx, const anet_flat_params *params, int64_t ba
                        double *vel_total, double *acc_total, double *jer_total, double *psi_total, double *dpsi_total);
 
 /* Along trajectories (psi = dpsi = 0, as in the reference): the piece location of anet_traj_eval, then velocity, acceleration and
- * jerk at each query and the forward map.  Per query 11 fields: thr, q0..q3, omg0..2, speed = |v|, tilt = acos(1 - 2 (q1^2 + q2^2)),
- * bdr = |omg| -- the last three and thr are what process() publishes (learning_planning.cpp:249-251).
+ * jerk at each query and the forward map.  Per query 11 fields: thr, q0..q3, omg0..2, speed = |v|, the tilt angle (acos(1 - 2 (q1^2 + q2^2)),
+ * computed as 2 atan2(sqrt(q1^2 + q2^2), sqrt(q0^2 + q3^2)), which keeps small tilts), bdr = |omg| -- the last three and thr are what process() publishes (learning_planning.cpp:249-251).
  * out: [nq*11][ld] (dev, query-major then field) / [batch][nq][11] (host).                                                    */
 #define ANET_FLAT_STATE_FIELDS 11
 int anet_traj_flat_states_dev(anet_ctx *ctx, const anet_flat_params *params, int s, int n_pieces, int64_t batch, int64_t ld,

@@ -60,6 +60,14 @@ def backward(vel, acc, jer, psi, dpsi, thr_grad, quat_grad, omg_grad, **par):
     return [g.numpy() for g in torch.autograd.grad(loss, ins)]
 
 
+def tilt_of_quat(q):
+    """Tilt angle of a unit quaternion (w, x, y, z): sin^2(tilt/2) = x^2 + y^2, cos^2(tilt/2) = w^2 + z^2.  Equal to
+    acos(1 - 2 (x^2 + y^2)), the expression process() publishes, but accurate at small tilts (where 1 - 2 (x^2 + y^2) rounds the
+    tilt away) and finite next to inversion."""
+    q = _t(q)
+    return 2.0 * torch.atan2(torch.sqrt(q[..., 1] ** 2 + q[..., 2] ** 2), torch.sqrt(q[..., 0] ** 2 + q[..., 3] ** 2))
+
+
 def quat_to_rot(q):
     """Rotation matrix of a unit quaternion (w, x, y, z), (..., 3, 3)."""
     q = _t(q)

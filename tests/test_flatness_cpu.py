@@ -44,7 +44,7 @@ def test_restatement_attitude_identities():
     assert float((quat.norm(dim=-1) - 1.0).abs().max()) <= 1e-14
     R = fnp.quat_to_rot(quat)
     assert float((R[:, :, 2] - z).abs().max()) <= 1e-14                 # the body z axis is the thrust direction
-    tilt_q = torch.acos(1.0 - 2.0 * (quat[:, 1] ** 2 + quat[:, 2] ** 2))
+    tilt_q = fnp.tilt_of_quat(quat)
     assert float((tilt_q - torch.acos(z[:, 2])).abs().max()) <= 1e-13
     # the body x axis has the heading psi: its projection on the horizontal plane before the tilt
     thr0, quat0, _, _ = fnp.forward(v, a, j)

@@ -3,8 +3,11 @@ tests/test_flatness_cpu.py): the pointwise map and its adjoint, states and sampl
 tilt / body-rate penalty with its partial and total gradients, the accumulate contract, the torch layer, the host L-BFGS on
 the composed objective and the C++ facade.
 
-States are drawn inside the planner's boxes (|v| <= 4, |a| <= 6 per axis) and trajectories are slowed down until they stay
-inside them, so zu_3 >= 0.8 > 0 everywhere and no case has to be left out for the singular attitude."""
+In tests 1 to 11 states are drawn inside the planner's boxes (|v| <= 4, |a| <= 6 per axis) and trajectories are slowed down
+until they stay inside them, so zu_3 >= 0.8 > 0 everywhere and no case has to be left out for the singular attitude.  Tests
+12 to 14 leave the boxes: they compare all five kernels with the 70-digit reference of tests/flatness_mp.py on the families
+of tests/golden/flatness_cases.npz (hover, small tilt, fast, slow, free fall, towards inversion, other vehicles), every
+output against a bound derived before any run."""
 import json
 import math
 import os
@@ -15,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import flatness_mp as fmp
 from tests import flatness_np as fnp
 from tests.util import random_problem
 
@@ -133,7 +137,7 @@ def test_traj_flat_states(anet_ctx, s, N):
     v, a, j = (aa.traj_eval(co, T, tq, d, ctx=anet_ctx) for d in (1, 2, 3))
     rt, rq, ro, _ = fnp.forward(v, a, j)
     ref = np.concatenate([rt.numpy()[..., None], rq.numpy(), ro.numpy(), np.linalg.norm(v, axis=-1)[..., None],
-                          torch.acos(1.0 - 2.0 * (rq[..., 1] ** 2 + rq[..., 2] ** 2)).numpy()[..., None],
+                          fnp.tilt_of_quat(rq).numpy()[..., None],
                           np.linalg.norm(ro.numpy(), axis=-1)[..., None]], -1)
     _close(got, ref, 1e-12, f"states s={s} N={N}")
     # Trajectory.getFlatState is the same call for one trajectory
@@ -152,7 +156,7 @@ def test_traj_flat_extrema_and_limits(anet_ctx, s, N):
     got = aa.traj_flat_extrema(fm, co, T, res, ctx=anet_ctx)
     sm = fnp.traj_samples(co, T, res, closed=True)
     ref = np.stack([sm["thr"].amin((1, 2)).numpy(), sm["thr"].amax((1, 2)).numpy(),
-                    torch.acos(sm["cos_tilt"].amin((1, 2))).numpy(), torch.sqrt(sm["bdr2"].amax((1, 2))).numpy()], 1)
+                    fnp.tilt_of_quat(sm["quat"]).amax((1, 2)).numpy(), torch.sqrt(sm["bdr2"].amax((1, 2))).numpy()], 1)
     _close(got, ref, 1e-12, f"extrema s={s} N={N}")
     tr = aa.Trajectory(T[1], co[1], ctx=anet_ctx)
     lo, hi, tilt, bdr = tr.getFlatExtrema(fm, res)
@@ -371,3 +375,178 @@ def test_cpp_flatness_program(anet_ctx):
     rt, rq, ro, _ = fnp.forward(v, a, j, psi, dpsi)
     _close(np.concatenate([thr[:, None], quat, omg], 1), np.concatenate([rt.numpy()[:, None], rq.numpy(), ro.numpy()], 1), 1e-12,
            "facade against the restatement")
+
+
+# 12 --------------------------------------------------------------------------------------------
+# The kernels against the 70-digit reference of tests/flatness_mp.py, read from tests/golden/flatness_cases.npz: every output of
+# every lane within K eps scale (1 + 1/delta) of its own reference (K by counting roundings, scale and delta from the reference
+# alone; flatness_mp's docstring and DESIGN.md 8f).  Nothing is compared relative to a batch maximum and no case is left out.
+
+@pytest.fixture(scope="module")
+def fx():
+    return fmp.load()
+
+
+def _cycled(n_cases, n_lanes, shift=0):
+    """lane -> case with a stride coprime to the number of cases: every case on some lane, neighbours differ"""
+    stride = next(p for p in (7, 11, 13, 17, 5, 3, 1) if math.gcd(p, n_cases) == 1)
+    return (np.arange(n_lanes) * stride + shift) % n_cases
+
+
+def _ratios(got, ref, scale, delta, K):
+    """|got - ref| / bound per entry; a zero bound asks for equality; anything not finite is inf"""
+    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    bnd = np.broadcast_to(fmp.flat_bound(scale, delta, K), ref.shape)
+    err = np.abs(got - ref)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(bnd > 0.0, err / bnd, np.where(err == 0.0, 0.0, np.inf))
+    return np.where(np.isfinite(got), r, np.inf)
+
+
+def _report(what, fams, r, check=True):
+    """r (lanes, ...) -> prints the worst ratio per family and returns them; check: asserts all <= 1"""
+    r = np.asarray(r).reshape(len(fams), -1).max(1)
+    worst = {}
+    for f, x in zip(fams, r):
+        worst[str(f)] = max(worst.get(str(f), 0.0), float(x))
+    print(what + ", error / bound: " + ", ".join(f"{f} {x:.3g}" for f, x in worst.items()))
+    assert not check or max(worst.values()) <= 1.0, (what, worst)
+    return worst
+
+
+@pytest.mark.parametrize("yaw", [True, False])
+def test_flat_forward_backward_meet_the_mp_bounds(anet_ctx, fx, yaw):
+    import allocnet_amd as aa
+    n = 263                                                              # one full 256-lane block and a 7-lane tail
+    ld = aa.recommended_ld(n)
+    seen = 0
+    for veh in range(len(fx["vehicles"])):
+        cases = np.flatnonzero((fx["pt_veh"] == veh) & (fx["pt_yaw"] == yaw))
+        seen += len(cases)
+        k = cases[_cycled(len(cases), n)]
+        par = aa.make_flat_params(*fx["vehicles"][veh])
+        v, a, j, g = fx["pt_v"][k], fx["pt_a"][k], fx["pt_j"][k], fx["pt_g"][k]
+        psi, dpsi = (fx["pt_psi"][k], fx["pt_dpsi"][k]) if yaw else (None, None)
+        dv, da, dj = _bm(v, ld), _bm(a, ld), _bm(j, ld)
+        dps, ddp = (_bm(psi, ld), _bm(dpsi, ld)) if yaw else (None, None)
+        thr, quat, omg = aa.flat_forward_dev(par, dv, da, dj, dps, ddp, n=n, ctx=anet_ctx)
+        got = np.c_[thr[:n].cpu().numpy(), quat[:, :n].T.cpu().numpy(), omg[:, :n].T.cpu().numpy()]
+        dl = fx["pt_delta"][k][:, None]
+        _report(f"forward yaw={yaw} vehicle {veh}", fx["pt_family"][k], _ratios(got, fx["pt_fwd"][k], fx["pt_fwd_scale"][k], dl, fmp.K_FWD))
+        out = aa.flat_backward_dev(par, dv, da, dj, dps, ddp, None, None, _bm(g[:, 0], ld), _bm(g[:, 1:5], ld), _bm(g[:, 5:8], ld),
+                                   n=n, ctx=anet_ctx)
+        _, vt, at, jt, pst, dpt = [(t[:, :n].T if t.dim() == 2 else t[:n]).cpu().numpy() for t in out]
+        gad = np.c_[vt, at, jt, pst, dpt]
+        _report(f"adjoint yaw={yaw} vehicle {veh}", fx["pt_family"][k], _ratios(gad, fx["pt_adj"][k], fx["pt_adj_scale"][k], dl, fmp.K_ADJ))
+        # exact hover: v = a = 0 and j != 0 give thr = m g and the tilt quaternion (1, 0, 0, 0) with no rounding at all
+        hov = np.flatnonzero((fx["pt_family"][k] == "hover") & (np.abs(v).sum(1) + np.abs(a).sum(1) == 0.0))
+        if veh == 0:
+            assert len(hov) >= 1 and np.abs(j[hov]).min() > 0.0
+            assert (got[hov, 0] == fx["vehicles"][0][0] * fx["vehicles"][0][1]).all() and (got[hov, 0] == fx["pt_fwd"][k][hov, 0]).all()
+            assert (got[hov, 2] == 0.0).all() and (got[hov, 3] == 0.0).all()
+            if not yaw:
+                assert (got[hov, 1:5] == [1.0, 0.0, 0.0, 0.0]).all()
+        # the host forms: the same bits at n = 1 and n = 3
+        for m in (1, 3):
+            ht, hq, ho = aa.flat_forward(par, v[:m], a[:m], j[:m], psi[:m] if yaw else None, dpsi[:m] if yaw else None, ctx=anet_ctx)
+            assert np.array_equal(np.c_[ht, hq, ho], got[:m])
+            hb = aa.flat_backward(par, v[:m], a[:m], j[:m], psi[:m] if yaw else None, dpsi[:m] if yaw else None, None, None,
+                                  g[:m, 0], g[:m, 1:5], g[:m, 5:8], ctx=anet_ctx)
+            assert np.array_equal(np.c_[hb[1], hb[2], hb[3], hb[4], hb[5]], gad[:m])
+    assert seen == 64                                                    # every case of this half went through a launch
+
+
+# 13 --------------------------------------------------------------------------------------------
+def _piece_launch(anet_ctx, fx, s, cases, lane_case, B, N, accumulate=False, into=None):
+    """One launch of anet_minco_flat_partial_grads_dev with slot (b, i) holding the fixture case cases[lane_case[b, i]] (all of
+    one limit set) -> gC (B, N, 3, D), gT (B, N), pc (B, N) and the case of every slot."""
+    D = 2 * s
+    which = cases[lane_case]                                              # (B, N)
+    pieces = fx["pn_piece"][which]
+    co = fx["pc_cm"][pieces][..., 8 - D:]                                 # (B, N, 3, D)
+    T = fx["pc_T"][pieces]
+    pen = fx["pn_pen"][cases[0]]
+    assert (fx["pn_pen"][cases] == pen).all()
+    kw = dict(w_thr=pen[0], w_tilt=pen[1], w_bdr=pen[2], mu=pen[3], thr_min=pen[4], thr_max=pen[5], tilt_max=pen[6], bdr_max=pen[7])
+    (gC, gT, pc), ld, _, _ = _flat_partials(anet_ctx, _penalty_of(kw, int(pen[8])), s, N, B, np.ascontiguousarray(co), T,
+                                            accumulate=accumulate, into=into)
+    return (gC[:, :B].T.cpu().numpy().reshape(B, N, 3, D), gT[:, :B].T.cpu().numpy(), pc[:, :B].T.cpu().numpy(), which, (gC, gT, pc), ld)
+
+
+def _check_pieces(what, fx, s, out):
+    gC, gT, pc, which = out[:4]
+    D = 2 * s
+    dl = fx["pn_delta"][which]
+    r = np.concatenate([_ratios(gC, fx["pn_gC"][which][..., 8 - D:], fx["pn_gC_scale"][which][..., 8 - D:], dl[..., None, None],
+                                fmp.K_PIECE).reshape(which.size, -1),
+                        _ratios(gT, fx["pn_gT"][which], fx["pn_gT_scale"][which], dl, fmp.K_PIECE).reshape(-1, 1),
+                        _ratios(pc, fx["pn_pc"][which], fx["pn_pc_scale"][which], dl, fmp.K_PIECE).reshape(-1, 1)], 1)
+    _report(what, fx["pn_family"][which].ravel(), r)
+
+
+@pytest.mark.parametrize("res", [1, 4])
+@pytest.mark.parametrize("s", [3, 4])
+def test_flat_partial_grads_meet_the_mp_bounds(anet_ctx, fx, s, res):
+    """piece_cost, every gdC entry and gdT of every (lane, piece) against their own bounds, one launch per limit set, in two
+    arrangements: cycled (every 64-lane wave mixes pieces with and without an active row) and sorted (lanes 0..127, two whole
+    waves, hold only pieces without an active row, so those waves take the wave-uniform skip of the adjoint, next to whole
+    waves of active pieces)."""
+    B, N = 263, 3
+    groups = np.unique(fx["pn_group"][(fx["pn_s"] == s) & (fx["pn_res"] == res)])
+    assert len(groups) == 3
+    skipping_waves = 0
+    for grp in groups:
+        cases = np.flatnonzero(fx["pn_group"] == grp)
+        nc = len(cases)
+        name = str(fx["pn_family"][cases[0]]).split("/")[0]
+        cyc = (_cycled(nc, B)[:, None] + np.arange(N)[None]) % nc
+        _check_pieces(f"pieces s={s} res={res} {name} cycled", fx, s, _piece_launch(anet_ctx, fx, s, cases, cyc, B, N))
+        quiet = np.flatnonzero(fx["pn_pc"][cases] == 0.0)
+        loud = np.flatnonzero(fx["pn_pc"][cases] > 0.0)
+        if len(quiet) and len(loud):
+            srt = np.empty((B, N), dtype=np.int64)
+            srt[:128] = quiet[(_cycled(len(quiet), 128)[:, None] + np.arange(N)[None]) % len(quiet)]
+            srt[128:] = loud[(_cycled(len(loud), B - 128)[:, None] + np.arange(N)[None]) % len(loud)]
+            out = _piece_launch(anet_ctx, fx, s, cases, srt, B, N)
+            _check_pieces(f"pieces s={s} res={res} {name} sorted", fx, s, out)
+            assert (out[2][:128] == 0.0).all() and (out[0][:128] == 0.0).all() and (out[2][128:192] > 0.0).any()
+            skipping_waves += 1
+        if name == "linear":
+            # accumulate = 1 onto a known buffer: one unfused addition of the same share
+            plain = _piece_launch(anet_ctx, fx, s, cases, cyc, B, N)
+            ld = plain[5]
+            into = tuple(torch.full((r, ld), 0.625, dtype=torch.float64, device=DEV) for r in (N * 3 * 2 * s, N, N))
+            _piece_launch(anet_ctx, fx, s, cases, cyc, B, N, accumulate=True, into=into)
+            for acc, share in zip(into, plain[4]):
+                assert torch.equal(acc[:, :B], 0.625 + share[:, :B]) and (acc[:, B:] == 0.625).all()
+            # one trajectory, ld = 1
+            one = np.flatnonzero(fx["pn_pc"][cases] > 0.0)[:1]
+            _check_pieces(f"pieces s={s} res={res} {name} B=1", fx, s, _piece_launch(anet_ctx, fx, s, cases, np.repeat(one, N)[None], 1, N))
+    assert skipping_waves >= 2                                           # the linear and the cubic set
+
+
+# 14 --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("B", [71, 263])
+@pytest.mark.parametrize("s", [3, 4])
+def test_traj_flat_states_and_extrema_meet_the_mp_bounds(anet_ctx, fx, s, B):
+    """Every field of every query and all four extrema (64 x 4 workgroups with their LDS reduction, and a tail), tilt and speed
+    included; nothing is NaN on any family, the tilted one (delta down to 1e-3) included."""
+    import allocnet_amd as aa
+    D = 2 * s
+    trs = np.flatnonzero((fx["tr_s"] == 0) | (fx["tr_s"] == s))
+    assert len(trs) == 12
+    k = trs[_cycled(len(trs), B)]
+    pieces = fx["tr_piece"][k]                                             # (B, 3)
+    co, T, tq = np.ascontiguousarray(fx["pc_cm"][pieces][..., 8 - D:]), fx["pc_T"][pieces], fx["tr_tq"][k]
+    fm = aa.FlatnessMap(ctx=anet_ctx)
+    got = aa.traj_flat_states(fm, co, T, tq, ctx=anet_ctx)
+    ext = aa.traj_flat_extrema(fm, co, T, 4, ctx=anet_ctx)
+    print(f"not finite: {int((~np.isfinite(got)).sum())} state fields, {int((~np.isfinite(ext)).sum())} extrema")
+    ws = _report(f"states s={s} B={B}", fx["tr_family"][k], check=False,
+                 r=_ratios(got, fx["tr_state"][k], fx["tr_state_scale"][k], fx["tr_state_delta"][k][..., None], fmp.K_TRAJ))
+    we = _report(f"extrema s={s} B={B}", fx["tr_family"][k], check=False,
+                 r=_ratios(ext, fx["tr_ext"][k], fx["tr_ext_scale"][k], fx["tr_ext_delta"][k][:, None], fmp.K_TRAJ))
+    assert np.isfinite(got).all() and np.isfinite(ext).all()
+    assert max(ws.values()) <= 1.0 and max(we.values()) <= 1.0, (ws, we)
+    hov = np.flatnonzero(fx["tr_family"][k] == "hover")
+    assert len(hov) and (got[hov][:, :, 9] == 0.0).all() and (ext[hov, 2] == 0.0).all()      # no tilt at exact hover
