@@ -119,6 +119,8 @@ PROTOTYPES = {
     "anet_voxel_surface_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "anet_voxel_surf_points_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "anet_voxel_query_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "anet_traj_voxel_hit_dev": (c_int, [c_void_p, c_int, c_int, c_int64, c_int64] + [c_void_p] * 7),
+    "anet_traj_voxel_hit": (c_int, [c_void_p, c_int, c_int, c_int64] + [c_void_p] * 6),
     "anet_voxel_gather_workspace": (c_int64, [c_int64, c_int64]),
     "anet_voxel_gather_boxes_dev": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                                             c_void_p, c_void_p]),

@@ -16,6 +16,7 @@
 //   api_polytope.hip   vertex enumeration of polytopes (geo_utils::enumerateVs)
 //   api_sfc.hip        waypoints as vertex weights of corridor overlaps: the transform, its inverse, the constrained MINCO L-BFGS
 //   api_margin.hip     exact margins of trajectories against corridor and box-limit rows
+//   api_voxel_hit.hip  exact first collision of trajectories with the voxel map
 //   piece_grad_unit.hip, qp_ipm_fuse_unit.hip: kernels scheduled for ILP, reached through launch functions
 // Only what two or more units use is here.  Nothing here is exported: the library's dynamic symbols stay the anet_* entry
 // points (and the kernels).
@@ -186,6 +187,16 @@ inline int check_solve_args(anet_ctx *ctx, int s, int c, int n_pieces, int64_t b
     return fail(ctx, ANET_ERR_INVALID, "piece count must be in [1, ANET_MAX_PIECES]");
   if (batch < 0) return fail(ctx, ANET_ERR_INVALID, "negative batch");
   return ANET_OK;
+}
+
+// the grid every voxel entry point accepts: sizes >= 1, fewer than 2^31 voxels, a finite origin, a finite scale > 0
+inline bool voxel_grid_ok(const anet_voxel_grid *g) {
+  if (!g || g->size[0] < 1 || g->size[1] < 1 || g->size[2] < 1) return false;
+  if ((int64_t)g->size[0] * g->size[1] * g->size[2] >= ((int64_t)1 << 31)) return false;
+  if (!(g->scale > 0.0) || !(fabs(g->scale) < INFINITY)) return false;
+  for (int c = 0; c < 3; ++c)
+    if (!(fabs(g->origin[c]) < INFINITY)) return false;
+  return true;
 }
 
 inline int check_penalty(anet_ctx *ctx, const anet_penalty *pen) {

@@ -10,11 +10,7 @@ extern "C" {
 // ---- voxel map (csrc/voxel_kernels.h) -----------------------------------------------------------
 static bool vox_grid_of(const anet_voxel_grid *g, anet::VoxGrid *out) {
 #pragma clang fp contract(off)
-  if (!g || g->size[0] < 1 || g->size[1] < 1 || g->size[2] < 1) return false;
-  if ((int64_t)g->size[0] * g->size[1] * g->size[2] >= ((int64_t)1 << 31)) return false;
-  if (!(g->scale > 0.0) || !std::isfinite(g->scale)) return false;
-  for (int c = 0; c < 3; ++c)
-    if (!std::isfinite(g->origin[c])) return false;
+  if (!voxel_grid_ok(g)) return false;
   out->sx = g->size[0]; out->sy = g->size[1]; out->sz = g->size[2];
   out->scale = g->scale;
   const int step[3] = {1, g->size[0], g->size[0] * g->size[1]};

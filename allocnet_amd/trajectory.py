@@ -122,6 +122,76 @@ def _stack_hpolys(hPolys):
     return out
 
 
+HIT_FREE, HIT_OUTSIDE, HIT_INVALID = -1, -2, -3
+
+
+def traj_voxel_hit(coeffs, T, vm, ctx=None):
+    """Exact first collision of every piece with the VoxelMap vm (anet_traj_voxel_hit): t_hit = inf{t in [0, T_i]: vm.query(p_i(t))},
+    +inf for a free piece, NaN for a piece with a non-finite input or a negative duration.  coeffs (B,N,3,D), T (B,N) ->
+    (t_hit (B,N), voxel (B,N) int32: the linear index x + sx (y + sy z) of the blocked voxel entered, HIT_FREE, HIT_OUTSIDE when
+    the curve left the map, HIT_INVALID; HIT_INVALID with a finite t_hit: undecided from t_hit on, treat as a hit)."""
+    import torch
+    ctx = ctx or vm.ctx
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+    T = np.ascontiguousarray(T, dtype=np.float64)
+    B, N, three, D = coeffs.shape
+    if three != 3 or T.shape != (B, N):
+        raise ValueError("shape mismatch")
+    t_hit = np.empty((B, N))
+    voxel = np.empty((B, N), dtype=np.int32)
+    torch.cuda.current_stream(vm.device).synchronize()      # the map's fills and dilations run there, the call on the context's stream
+    ctx.check(ctx.lib.anet_traj_voxel_hit(ctx.handle, D // 2, N, B, _ptr(coeffs), _ptr(T), ctypes.byref(vm._grid),
+                                          ctypes.c_void_p(vm.voxels_dev.data_ptr()), _ptr(t_hit), _ptr(voxel)))
+    return t_hit, voxel
+
+
+def traj_voxel_hit_dev(coeffs, T, vm, s, n_pieces, batch, t_hit=None, voxel=None, ctx=None):
+    """anet_traj_voxel_hit_dev on batch-minor CUDA tensors, asynchronous on torch's current stream: coeffs (N*3*2s, ld), T (N, ld)
+    float64 -> (t_hit (N, ld) float64, voxel (N, ld) int32); columns from `batch` on are not touched.  voxel=False: not wanted."""
+    import torch
+    ctx = ctx or vm.ctx
+    ld = int(T.shape[1])
+    if coeffs.dtype != torch.float64 or T.dtype != torch.float64 or not (coeffs.is_contiguous() and T.is_contiguous()):
+        raise ValueError("traj_voxel_hit_dev: contiguous float64 tensors expected")
+    if tuple(coeffs.shape) != (n_pieces * 6 * s, ld) or T.shape[0] != n_pieces:
+        raise ValueError("shape mismatch")
+    if t_hit is None:
+        t_hit = torch.empty((n_pieces, ld), dtype=torch.float64, device=T.device)
+    if voxel is None:
+        voxel = torch.empty((n_pieces, ld), dtype=torch.int32, device=T.device)
+    for out, dt in ((t_hit, torch.float64), (voxel, torch.int32)):
+        if out is not False and (out.dtype != dt or tuple(out.shape) != (n_pieces, ld) or not out.is_contiguous()):
+            raise ValueError("traj_voxel_hit_dev: outputs are contiguous (N, ld) tensors, float64 and int32")
+    p = lambda x: ctypes.c_void_p(x.data_ptr())
+    stream = ctypes.c_void_p(torch.cuda.current_stream(T.device).cuda_stream)
+    ctx.check(ctx.lib.anet_traj_voxel_hit_dev(ctx.handle, int(s), int(n_pieces), int(batch), ld, p(coeffs), p(T),
+                                              ctypes.byref(vm._grid), p(vm.voxels_dev), p(t_hit),
+                                              None if voxel is False else p(voxel), stream))
+    return t_hit, (None if voxel is False else voxel)
+
+
+def first_collision_of(t_hit, voxel, T):
+    """The per-piece answers of traj_voxel_hit -> per trajectory (t (B,) global time, piece (B,) int32, voxel (B,) int32): the
+    first piece whose t_hit is not +inf (a NaN piece counts: nothing is known from its start on); free: (inf, -1, HIT_FREE)."""
+    t_hit = np.asarray(t_hit, dtype=np.float64)
+    T = np.asarray(T, dtype=np.float64)
+    B, N = t_hit.shape
+    start = np.concatenate([np.zeros((B, 1)), np.cumsum(T, axis=1)[:, :-1]], axis=1)
+    found = ~(t_hit == np.inf)
+    piece = np.where(found.any(axis=1), found.argmax(axis=1), -1).astype(np.int32)
+    rows, col = np.arange(B), np.maximum(piece, 0)
+    t = np.where(piece >= 0, start[rows, col] + t_hit[rows, col], np.inf)
+    vox = np.where(piece >= 0, np.asarray(voxel)[rows, col], HIT_FREE).astype(np.int32)
+    return t, piece, vox
+
+
+def traj_first_collision(coeffs, T, vm, ctx=None):
+    """First collision of every trajectory with the VoxelMap vm: (t (B,): global time, the earlier durations plus t_hit; piece (B,)
+    int32; voxel (B,) int32 as in traj_voxel_hit).  A free trajectory has t = inf, piece = -1, voxel = HIT_FREE."""
+    t_hit, voxel = traj_voxel_hit(coeffs, T, vm, ctx=ctx)
+    return first_collision_of(t_hit, voxel, T)
+
+
 def piece_normalized_coeffs(coeffs, T, deriv, ctx=None):
     """Piece::normalizePosCoeffMat / normalizeVelCoeffMat / normalizeAccCoeffMat (trajectory.hpp:135-171) for a batch of pieces:
     coefficients of position (deriv 0), velocity (1) or acceleration (2) in normalised time.  coeffs (P,3,D), T (P,) -> (P,3,D-deriv)."""
@@ -200,6 +270,12 @@ class Piece:
         """Exact max over the rows a.x <= b of hPoly (M, 4) and over the piece of a . p(t) - b (no counterpart in the reference)."""
         return float(traj_row_margin(self.coeffMat[None, None], np.array([[self.duration]]), _stack_hpolys([hPoly]), 0,
                                      ctx=self._ctx)[0][0, 0])
+
+    def getFirstCollision(self, vm):
+        """(t, voxel): the first local time at which the piece is in a blocked voxel of the VoxelMap vm or outside it (inf: never)
+        and the voxel's linear index (HIT_FREE, HIT_OUTSIDE, HIT_INVALID); exact, not sampled (no counterpart in the reference)."""
+        t, v = traj_voxel_hit(self.coeffMat[None, None], np.array([[self.duration]]), vm, ctx=self._ctx)
+        return float(t[0, 0]), int(v[0, 0])
 
 
 class Trajectory:
@@ -307,6 +383,21 @@ class Trajectory:
         vel = traj_row_margin(co, T, np.broadcast_to(box_rows(max_vel), shape), 1, ctx=self._ctx)[0]
         acc = traj_row_margin(co, T, np.broadcast_to(box_rows(max_acc), shape), 2, ctx=self._ctx)[0]
         return bool(vel.max() <= 0.0 and acc.max() <= 0.0)
+
+    # --- exact first collision with the voxel map (no counterpart in the reference) -----------------------------------
+    def getFirstCollision(self, vm, per_piece=False):
+        """(t, piece, voxel): the global time of the first collision with the VoxelMap vm (inf: none), its piece (-1) and the
+        voxel's linear index (HIT_FREE, HIT_OUTSIDE, HIT_INVALID); per_piece=True: the arrays (t_hit, voxel) over the pieces,
+        t_hit in local time."""
+        co, T = self._arrays()
+        t_hit, voxel = traj_voxel_hit(co, T, vm, ctx=self._ctx)
+        if per_piece:
+            return t_hit[0], voxel[0]
+        t, piece, vox = first_collision_of(t_hit, voxel, T)
+        return float(t[0]), int(piece[0]), int(vox[0])
+
+    def checkCollisionFree(self, vm):
+        return self.getFirstCollision(vm)[1] < 0
 
     # --- the vehicle's own terms: thrust, attitude, body rate through the flatness map (flatness.py) ---------------
     def getFlatState(self, t, flatmap):

@@ -832,6 +832,28 @@ int anet_voxel_surf_points_dev(anet_ctx *ctx, const anet_voxel_grid *grid, const
 /* query: out[i] = 1 when position i (pos [n][3]) is outside the map or in a voxel != 0, else 0                      */
 int anet_voxel_query_dev(anet_ctx *ctx, const anet_voxel_grid *grid, const uint8_t *voxels, const double *pos, int64_t n,
                          uint8_t *out, void *stream);
+/* Exact first collision of every piece with the map (no counterpart in the reference, which has no trajectory-against-map test):
+ *     t_hit[i] = inf { t in [0, T_i] : blocked(p_i(t)) },  blocked(p) <=> anet_voxel_query_dev answers 1 for p
+ * (outside the map, or in a voxel != 0; cell = ((p - origin) / scale) truncated toward zero, so cell 0 spans -1 < q < 1), +inf
+ * when the piece is free: the minimum over the pieces of (earlier durations + t_hit) is the trajectory's first collision.  Not
+ * sampled: a curve that clips a voxel between two samples is found.  coeffs, T: the layouts of anet_traj_eval[_dev]; voxels: the
+ * DEVICE byte grid in both forms; t_hit: double [N][ld] (dev) / [batch][N] (host); voxel (may be NULL): int32 of the same shape,
+ * the linear index of the blocked voxel entered, ANET_HIT_FREE, ANET_HIT_OUTSIDE (the curve left the map) or ANET_HIT_INVALID.
+ * A curve that starts blocked has t_hit = 0; a piece with T_i == 0 is the point p_i(0).  A NaN or infinite coefficient or
+ * duration, or T_i < 0, gives t_hit = NaN and ANET_HIT_INVALID for that piece only.  ANET_HIT_INVALID with a FINITE t_hit: the
+ * kernel's bounded search ran out; the piece is free before t_hit and undecided from there on (treat as a hit).  A bad grid
+ * (non-finite fields, scale <= 0, sizes < 1) is ANET_ERR_INVALID.  Accuracy (csrc/voxel_hit_kernels.h):
+ * |t_hit - t*| <= T_i 2^-32 + 32 eps (sum_k |u_k| + |q_plane|) / |dq/dtau| T_i on the crossed axis, u the coefficients of q in
+ * normalised time; a voxel penetrated deeper than tol_pos is never missed, one farther than tol_pos away never reported.
+ * The host form runs on the context's stream: the map must be complete (its stream synchronised) before the call. */
+#define ANET_HIT_FREE (-1)
+#define ANET_HIT_OUTSIDE (-2)
+#define ANET_HIT_INVALID (-3)
+int anet_traj_voxel_hit_dev(anet_ctx *ctx, int s, int n_pieces, int64_t batch, int64_t ld, const double *coeffs, const double *T,
+                            const anet_voxel_grid *grid, const uint8_t *voxels, double *t_hit, int32_t *voxel, void *stream);
+int anet_traj_voxel_hit(anet_ctx *ctx, int s, int n_pieces, int64_t batch, const double *coeffs, const double *T,
+                        const anet_voxel_grid *grid, const uint8_t *voxels /* DEVICE: the map lives there */, double *t_hit,
+                        int32_t *voxel);
 /* convexCover's per-segment selection: for box k (bd [n_boxes][6][4], the layout of anet_firi's bd), the points p of
  * points [n_points][3] with max_r(bd[k][r][:3] . p + bd[k][r][3]) < 0, in their order, into out [n_boxes][max_points][3]
  * (rows past the count untouched); n_out[k] = the true count, which may exceed max_points.                           */
