@@ -124,6 +124,9 @@ PROTOTYPES = {
     "anet_voxel_gather_workspace": (c_int64, [c_int64, c_int64]),
     "anet_voxel_gather_boxes_dev": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                                             c_void_p, c_void_p]),
+    "anet_traj_clearance_dev": (c_int, [c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int, c_int64] +
+                                [c_void_p] * 6),
+    "anet_traj_clearance": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_int64] + [c_void_p] * 5),
     "anet_voxel_path_workspace": (c_int64, [c_void_p, c_int64]),
     "anet_voxel_path_field_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                           c_void_p]),

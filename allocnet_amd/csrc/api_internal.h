@@ -17,6 +17,7 @@
 //   api_sfc.hip        waypoints as vertex weights of corridor overlaps: the transform, its inverse, the constrained MINCO L-BFGS
 //   api_margin.hip     exact margins of trajectories against corridor and box-limit rows
 //   api_voxel_hit.hip  exact first collision of trajectories with the voxel map
+//   api_clearance.hip  exact clearance of trajectories to obstacle points
 //   piece_grad_unit.hip, qp_ipm_fuse_unit.hip: kernels scheduled for ILP, reached through launch functions
 // Only what two or more units use is here.  Nothing here is exported: the library's dynamic symbols stay the anet_* entry
 // points (and the kernels).

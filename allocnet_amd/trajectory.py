@@ -192,6 +192,123 @@ def traj_first_collision(coeffs, T, vm, ctx=None):
     return first_collision_of(t_hit, voxel, T)
 
 
+def _is_voxel_map(x):
+    return hasattr(x, "surf_points_dev") and hasattr(x, "voxels_dev")
+
+
+def traj_clearance(coeffs, T, points, counts=None, ctx=None):
+    """Exact per-piece clearance to obstacle points (anet_traj_clearance): the minimum over the finite points q of a piece's set
+    and over t in [0, T_i] of ||p_i(t) - q||, metres; +inf: no finite point; NaN: a non-finite input of that piece or T_i < 0.
+    coeffs (B,N,3,D), T (B,N); points (P,3): one cloud shared by every piece, or (N,Pmax,3): piece i against points[i] (the
+    output of VoxelMap.gather_boxes), numpy or a CUDA tensor; a VoxelMap stands for its surface points.  counts: the number of
+    points of each set, (N,) or a scalar for a shared cloud, clamped to the set's rows; None: all of them.
+    -> (clearance (B,N), point (B,N) int32: a minimising point's index in its set or -1, t (B,N): its local time)."""
+    if _is_voxel_map(points):
+        ctx = ctx or points.ctx
+        points = points.surf_points_dev()
+    ctx = ctx or default_context()
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+    T = np.ascontiguousarray(T, dtype=np.float64)
+    B, N, three, D = coeffs.shape
+    if three != 3 or T.shape != (B, N) or D not in (4, 6, 8):
+        raise ValueError("shape mismatch")
+    if not isinstance(points, np.ndarray) and hasattr(points, "is_cuda"):
+        import torch
+        if not points.is_cuda:
+            points = points.numpy()
+        else:       # the cloud stays where it is: the batch goes to the device instead
+            dev = points.device
+            co = torch.from_numpy(coeffs.reshape(B, N * 3 * D).T.copy()).to(dev)
+            Td = torch.from_numpy(T.T.copy()).to(dev)
+            if counts is not None and not isinstance(counts, torch.Tensor):
+                counts = torch.from_numpy(np.atleast_1d(np.asarray(counts, dtype=np.int32))).to(dev)
+            c, p, t = traj_clearance_dev(co, Td, points, D // 2, N, B, counts=counts, ctx=ctx)
+            return c.cpu().numpy().T.copy(), p.cpu().numpy().T.copy(), t.cpu().numpy().T.copy()
+    points = np.ascontiguousarray(points, dtype=np.float64)
+    if points.ndim == 2 and points.shape[1] == 3:
+        n_sets, pmax = 1, points.shape[0]
+    elif points.ndim == 3 and points.shape[0] == N and points.shape[2] == 3:
+        n_sets, pmax = N, points.shape[1]
+    else:
+        raise ValueError("points: (P, 3) or (N, Pmax, 3)")
+    if counts is not None:
+        counts = np.ascontiguousarray(np.atleast_1d(counts), dtype=np.int32)
+        if counts.shape != (n_sets,):
+            raise ValueError("counts: one per set")
+    clearance = np.empty((B, N))
+    point = np.empty((B, N), dtype=np.int32)
+    t = np.empty((B, N))
+    ctx.check(ctx.lib.anet_traj_clearance(ctx.handle, D // 2, N, B, _ptr(coeffs), _ptr(T), n_sets, pmax, _ptr(points),
+                                          None if counts is None else _ptr(counts), _ptr(clearance), _ptr(point), _ptr(t)))
+    return clearance, point, t
+
+
+def traj_clearance_dev(coeffs, T, points, s, n_pieces, batch, counts=None, clearance=None, point=None, t=None, ctx=None):
+    """anet_traj_clearance_dev on batch-minor CUDA tensors, asynchronous on torch's current stream: coeffs (N*3*2s, ld), T (N, ld)
+    float64; points (P, 3) or (N, Pmax, 3) float64 CUDA (or a VoxelMap: its surface points), counts (n_sets,) int32 CUDA or None
+    -> (clearance (N, ld) float64, point (N, ld) int32, t (N, ld) float64); columns from `batch` on are not touched.
+    point=False / t=False: not wanted."""
+    import torch
+    if _is_voxel_map(points):
+        ctx = ctx or points.ctx
+        points = points.surf_points_dev()
+    ctx = ctx or default_context()
+    ld = int(T.shape[1])
+    if coeffs.dtype != torch.float64 or T.dtype != torch.float64 or not (coeffs.is_contiguous() and T.is_contiguous()):
+        raise ValueError("traj_clearance_dev: contiguous float64 tensors expected")
+    if tuple(coeffs.shape) != (n_pieces * 6 * s, ld) or T.shape[0] != n_pieces:
+        raise ValueError("shape mismatch")
+    if points.dtype != torch.float64 or not points.is_cuda or not points.is_contiguous():
+        raise ValueError("traj_clearance_dev: points is a contiguous float64 CUDA tensor")
+    if points.dim() == 2 and points.shape[1] == 3:
+        n_sets, pmax = 1, int(points.shape[0])
+    elif points.dim() == 3 and points.shape[0] == n_pieces and points.shape[2] == 3:
+        n_sets, pmax = int(n_pieces), int(points.shape[1])
+    else:
+        raise ValueError("points: (P, 3) or (N, Pmax, 3)")
+    if counts is not None and (counts.dtype != torch.int32 or not counts.is_cuda or counts.numel() != n_sets or not counts.is_contiguous()):
+        raise ValueError("traj_clearance_dev: counts is a contiguous int32 CUDA tensor, one per set")
+    if clearance is None:
+        clearance = torch.empty((n_pieces, ld), dtype=torch.float64, device=T.device)
+    if point is None:
+        point = torch.empty((n_pieces, ld), dtype=torch.int32, device=T.device)
+    if t is None:
+        t = torch.empty((n_pieces, ld), dtype=torch.float64, device=T.device)
+    for out, dt in ((clearance, torch.float64), (point, torch.int32), (t, torch.float64)):
+        if out is not False and (out.dtype != dt or tuple(out.shape) != (n_pieces, ld) or not out.is_contiguous()):
+            raise ValueError("traj_clearance_dev: outputs are contiguous (N, ld) tensors, float64 / int32 / float64")
+    if clearance is False:
+        raise ValueError("traj_clearance_dev: clearance is always written")
+    p = lambda x: None if (x is None or x is False) else ctypes.c_void_p(x.data_ptr())
+    stream = ctypes.c_void_p(torch.cuda.current_stream(T.device).cuda_stream)
+    ctx.check(ctx.lib.anet_traj_clearance_dev(ctx.handle, int(s), int(n_pieces), int(batch), ld, p(coeffs), p(T), n_sets, pmax,
+                                              p(points) if pmax else None, p(counts), p(clearance), p(point), p(t), stream))
+    return clearance, (None if point is False else point), (None if t is False else t)
+
+
+def clearance_of(clearance, point, t, T):
+    """The per-piece answers of traj_clearance -> per trajectory (clearance (B,), t (B,) global time, piece (B,) int32, point
+    (B,) int32): the piece with the smallest clearance.  A NaN piece makes the trajectory's clearance NaN (nothing is known
+    about that piece) and is the piece named; no finite point anywhere: (inf, 0, -1, -1)."""
+    clearance = np.asarray(clearance, dtype=np.float64)
+    T = np.asarray(T, dtype=np.float64)
+    B, N = clearance.shape
+    start = np.concatenate([np.zeros((B, 1)), np.cumsum(T, axis=1)[:, :-1]], axis=1)
+    bad = np.isnan(clearance)
+    piece = np.where(bad.any(axis=1), bad.argmax(axis=1), np.where(bad, np.inf, clearance).argmin(axis=1)).astype(np.int32)
+    rows = np.arange(B)
+    c = clearance[rows, piece]
+    none = c == np.inf
+    pt = np.where(none, -1, np.asarray(point)[rows, piece]).astype(np.int32)
+    tt = np.where(none | np.isnan(c), 0.0, start[rows, piece] + np.asarray(t)[rows, piece])
+    return c, tt, np.where(none, -1, piece).astype(np.int32), pt
+
+
+def clearance_at_least(clearance, min_dist):
+    """True when every clearance is >= min_dist; a NaN is False"""
+    return bool(np.all(np.asarray(clearance, dtype=np.float64) >= float(min_dist)))
+
+
 def piece_normalized_coeffs(coeffs, T, deriv, ctx=None):
     """Piece::normalizePosCoeffMat / normalizeVelCoeffMat / normalizeAccCoeffMat (trajectory.hpp:135-171) for a batch of pieces:
     coefficients of position (deriv 0), velocity (1) or acceleration (2) in normalised time.  coeffs (P,3,D), T (P,) -> (P,3,D-deriv)."""
@@ -276,6 +393,15 @@ class Piece:
         and the voxel's linear index (HIT_FREE, HIT_OUTSIDE, HIT_INVALID); exact, not sampled (no counterpart in the reference)."""
         t, v = traj_voxel_hit(self.coeffMat[None, None], np.array([[self.duration]]), vm, ctx=self._ctx)
         return float(t[0, 0]), int(v[0, 0])
+
+    def getClearance(self, points):
+        """(clearance, t, point): the exact smallest distance of the piece to the points (P, 3) (or a VoxelMap's surface), the local
+        time at which it is attained and the point's index; (inf, 0, -1) without a finite point (no counterpart in the reference)."""
+        c, p, t = traj_clearance(self.coeffMat[None, None], np.array([[self.duration]]), points, ctx=self._ctx)
+        return float(c[0, 0]), float(t[0, 0]), int(p[0, 0])
+
+    def checkClearance(self, points, min_dist):
+        return clearance_at_least(self.getClearance(points)[0], min_dist)
 
 
 class Trajectory:
@@ -398,6 +524,23 @@ class Trajectory:
 
     def checkCollisionFree(self, vm):
         return self.getFirstCollision(vm)[1] < 0
+
+    # --- exact clearance to obstacle points (no counterpart in the reference) ------------------------------------------
+    def getClearance(self, points, per_piece=False):
+        """(clearance, t, piece, point): the exact smallest distance, in metres, of the trajectory to the points -- (P, 3), one
+        cloud for every piece; (N, Pmax, 3), piece i against points[i]; or a VoxelMap, its surface -- the global time at which it
+        is attained, its piece and the point's index in its set; (inf, 0, -1, -1) without a finite point.  per_piece=True: the
+        arrays (clearance, point, t) over the pieces, t in local time."""
+        co, T = self._arrays()
+        c, p, t = traj_clearance(co, T, points, ctx=self._ctx)
+        if per_piece:
+            return c[0], p[0], t[0]
+        cc, tt, piece, pt = clearance_of(c, p, t, T)
+        return float(cc[0]), float(tt[0]), int(piece[0]), int(pt[0])
+
+    def checkClearance(self, points, min_dist):
+        """True when every piece keeps at least min_dist metres from every point, exactly; a NaN clearance is False."""
+        return clearance_at_least(self.getClearance(points, per_piece=True)[0], min_dist)
 
     # --- the vehicle's own terms: thrust, attitude, body rate through the flatness map (flatness.py) ---------------
     def getFlatState(self, t, flatmap):

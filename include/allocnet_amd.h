@@ -860,6 +860,32 @@ int anet_traj_voxel_hit(anet_ctx *ctx, int s, int n_pieces, int64_t batch, const
 int64_t anet_voxel_gather_workspace(int64_t n_boxes, int64_t n_points);
 int anet_voxel_gather_boxes_dev(anet_ctx *ctx, int64_t n_boxes, const double *bd, const double *points, int64_t n_points,
                                 int64_t max_points, void *work, double *out, int32_t *n_out, void *stream);
+/* Exact clearance of every piece to obstacle points (no counterpart in the reference): for piece i and the points q_j given for it
+ *     clearance[i] = min over finite points j, min over t in [0, T_i], of || p_i(t) - q_j ||      (Euclidean, metres)
+ * Not sampled: the minimum between two samples is found.  point[i] (may be NULL): a minimising point's index within its set, -1
+ * when the set has no finite point; t[i] (may be NULL): the local time of the minimum, 0 without a point.  Both are diagnostics
+ * specified by consistency, as row and t of anet_traj_row_margin are: || p_i(t) - q_point || reproduces clearance within the
+ * bound; there is no tie-breaking rule.  A piece without a finite point has clearance +inf.  A point with a non-finite coordinate
+ * is skipped, as setOccupied skips such records.  T_i == 0 is the point p_i(0).  A NaN or infinite coefficient or duration, or
+ * T_i < 0, gives clearance NaN, point -1 and t 0 for that piece only; so does a product c_k T_i^k that is not finite (an
+ * overflowing power of T_i also where c_k = 0).  Orders s = 2, 3, 4.
+ * coeffs, T: the layouts of anet_traj_row_margin[_dev]; clearance, point, t: [N][ld] (dev) / [batch][N] (host).
+ * points: [n_sets][max_points][3] doubles, on the DEVICE for the _dev form and on the HOST for the host form; counts: int32
+ * [n_sets] (same side), or NULL = max_points each; a count is clamped to [0, max_points].  n_sets is 1 (one cloud shared by every
+ * piece) or n_pieces (piece i uses set i: exactly the out / n_out pair of anet_voxel_gather_boxes_dev, whose counts may exceed
+ * max_points; hence the clamp); anything else is ANET_ERR_INVALID.  max_points == 0 is valid (points may be NULL): every piece
+ * gets +inf; max_points < 2^31.  batch == 0 returns ANET_OK after the argument checks.
+ * Accuracy (csrc/clearance_kernels.h): |clearance - exact| <= 32 eps scale + location term, scale = sum_ax (sum_k |u_ax,k| +
+ * |q_ax|), u the coefficients in normalised time; the location term is min(sqrt(2) E / sqrt(kappa), E^2 / (kappa d)) at an interior
+ * minimum, E = 16 eps scale ||u'|| + 32 eps d sum_ax sum_k k |u_ax,k| + 2 eps kappa, kappa = g''/2 there, and 0 at an end.
+ * The value is always an actual distance of the curve to a point of the set: never below the exact one by more than 32 eps scale. */
+int anet_traj_clearance_dev(anet_ctx *ctx, int s, int n_pieces, int64_t batch, int64_t ld, const double *coeffs, const double *T,
+                            int n_sets, int64_t max_points, const double *points /* [n_sets][max_points][3], device */,
+                            const int32_t *counts /* [n_sets] device, or NULL */, double *clearance, int32_t *point, double *t,
+                            void *stream);
+int anet_traj_clearance(anet_ctx *ctx, int s, int n_pieces, int64_t batch, const double *coeffs, const double *T, int n_sets,
+                        int64_t max_points, const double *points /* HOST */, const int32_t *counts /* HOST or NULL */,
+                        double *clearance, int32_t *point, double *t);
 
 /* ---- front-end route on the voxel map: sfc_gen::planPath ----------------------------------------------------------------
  * A collision-free polyline from s to g and its length, by a shortest-path field on the grid, a walk back along it and a

@@ -7,6 +7,13 @@
 // Exact, not sampled: a curve that clips a voxel between two samples is found.  The curve is blocked where voxelMap.query(pos) is
 // true: in a voxel != 0 or outside the map.  When it left the map (or the search was undecided: csrc/voxel_hit_kernels.h) there
 // is no voxel to name and id is (-1, -1, -1); `code`, where asked for, tells the cases apart (ANET_HIT_*).
+//
+// The exact clearance to obstacle points (anet_traj_clearance; no counterpart in the reference either):
+//     double t; int piece, point;
+//     double d = getClearance(traj, points, t, piece, point);   // points: std::vector<anet::Vec3>, or the map: its surface
+//     if (checkClearance(traj, voxelMap, 0.3)) ...               // every piece keeps 0.3 m from every surface point
+// d is the smallest distance in metres over the whole trajectory, t its global time, piece its piece and point the index of the
+// nearest point; +inf (t 0, piece -1, point -1) without a finite point, NaN when a piece has a non-finite coefficient.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -91,4 +98,101 @@ inline bool checkCollisionFree(const Piece<D> &pc, const voxel_map::VoxelMap &ma
   double t;
   voxel_map::Vec3i id;
   return !getFirstCollision(pc, map, t, id);
+}
+
+namespace anet {
+namespace detail {
+
+// n pieces of degree D against one shared cloud -> the smallest clearance; t in global time.  A NaN piece makes the answer NaN.
+template <int D>
+inline double clearance(const std::vector<double> &co, const std::vector<double> &T, const std::vector<anet::Vec3> &points, double &t,
+                        int &piece, int &point) {
+  const int n = (int)T.size();
+  std::vector<double> pts(points.size() * 3), cl((size_t)n), tt((size_t)n);
+  std::vector<int32_t> pi((size_t)n);
+  for (size_t j = 0; j < points.size(); ++j)
+    for (int c = 0; c < 3; ++c) pts[j * 3 + (size_t)c] = points[j](c);
+  anet::Context &ctx = anet::Context::thread_default();
+  ctx.check(anet_traj_clearance(ctx.get(), (D + 1) / 2, n, 1, co.data(), T.data(), 1, (int64_t)points.size(), pts.data(), nullptr,
+                                cl.data(), pi.data(), tt.data()));
+  double best = INFINITY, start = 0.0;
+  t = 0.0;
+  piece = point = -1;
+  for (int i = 0; i < n; ++i) {
+    const double c = cl[(size_t)i];
+    if (c != c) {  // nothing is known about this piece
+      t = 0.0;
+      piece = i;
+      point = -1;
+      return c;
+    }
+    if (c < best) {
+      best = c;
+      t = start + tt[(size_t)i];
+      piece = i;
+      point = pi[(size_t)i];
+    }
+    start += T[(size_t)i];
+  }
+  return best;
+}
+
+template <int D>
+inline void pack_pieces(const Trajectory<D> &traj, const char *who, std::vector<double> &co, std::vector<double> &T) {
+  const int n = traj.getPieceNum();
+  if (n < 1) throw anet::Error(ANET_ERR_INVALID, who);
+  co.resize((size_t)n * 3 * (D + 1));
+  T.resize((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    T[(size_t)i] = traj[i].getDuration();
+    const double *c = traj[i].getCoeffMat().data();
+    for (int k = 0; k < 3 * (D + 1); ++k) co[(size_t)i * 3 * (D + 1) + k] = c[k];
+  }
+}
+
+inline std::vector<anet::Vec3> surface_of(const voxel_map::VoxelMap &map) {
+  std::vector<anet::Vec3> pts;
+  map.getSurf(pts);
+  return pts;
+}
+
+}  // namespace detail
+}  // namespace anet
+
+// the smallest distance of the trajectory to the points: t its global time, piece the piece, point the nearest point's index
+template <int D>
+inline double getClearance(const Trajectory<D> &traj, const std::vector<anet::Vec3> &points, double &t, int &piece, int &point) {
+  std::vector<double> co, T;
+  anet::detail::pack_pieces<D>(traj, "getClearance: empty trajectory", co, T);
+  return anet::detail::clearance<D>(co, T, points, t, piece, point);
+}
+template <int D>
+inline double getClearance(const Trajectory<D> &traj, const voxel_map::VoxelMap &map, double &t, int &piece, int &point) {
+  return getClearance(traj, anet::detail::surface_of(map), t, piece, point);
+}
+// one piece: t in its local time
+template <int D>
+inline double getClearance(const Piece<D> &pc, const std::vector<anet::Vec3> &points, double &t, int &point) {
+  const double *c = pc.getCoeffMat().data();
+  std::vector<double> co(c, c + 3 * (D + 1)), T(1, pc.getDuration());
+  int piece = -1;
+  return anet::detail::clearance<D>(co, T, points, t, piece, point);
+}
+template <int D>
+inline double getClearance(const Piece<D> &pc, const voxel_map::VoxelMap &map, double &t, int &point) {
+  return getClearance(pc, anet::detail::surface_of(map), t, point);
+}
+
+// true when the clearance is at least min_dist (NaN: false)
+template <int D, class PointsOrMap>
+inline bool checkClearance(const Trajectory<D> &traj, const PointsOrMap &points, double min_dist) {
+  double t;
+  int piece, point;
+  return getClearance(traj, points, t, piece, point) >= min_dist;
+}
+template <int D, class PointsOrMap>
+inline bool checkClearance(const Piece<D> &pc, const PointsOrMap &points, double min_dist) {
+  double t;
+  int point;
+  return getClearance(pc, points, t, point) >= min_dist;
 }
