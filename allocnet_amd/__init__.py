@@ -11,6 +11,7 @@ from .trajectory import Piece, Trajectory, traj_eval, traj_cost, traj_cost_grad_
 from .trajectory import traj_row_margin, traj_qp_margins  # noqa: F401
 from .trajectory import traj_voxel_hit, traj_voxel_hit_dev, traj_first_collision, HIT_FREE, HIT_OUTSIDE, HIT_INVALID  # noqa: F401
 from .trajectory import traj_clearance, traj_clearance_dev  # noqa: F401
+from .trajectory import traj_separation, traj_separation_dev  # noqa: F401
 from . import lbfgs  # noqa: F401
 from .lbfgs import (lbfgs_parameter_t, lbfgs_strerror, lbfgs_mvie, lbfgs_minco, lbfgs_minco_dev,  # noqa: F401
                     launch_order_from_counts, lbfgs_optimize_dev, lbfgs_optimize)

@@ -127,6 +127,10 @@ PROTOTYPES = {
     "anet_traj_clearance_dev": (c_int, [c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int, c_int64] +
                                 [c_void_p] * 6),
     "anet_traj_clearance": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_int64] + [c_void_p] * 5),
+    "anet_traj_separation_dev": (c_int, [c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                 c_void_p, c_double] + [c_void_p] * 5),
+    "anet_traj_separation": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                             c_double] + [c_void_p] * 4),
     "anet_voxel_path_workspace": (c_int64, [c_void_p, c_int64]),
     "anet_voxel_path_field_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                           c_void_p]),

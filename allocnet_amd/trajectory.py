@@ -309,6 +309,93 @@ def clearance_at_least(clearance, min_dist):
     return bool(np.all(np.asarray(clearance, dtype=np.float64) >= float(min_dist)))
 
 
+def all_pairs(B):
+    """every (a, b) with a < b < B, sorted by a: (P, 2) int32 -- the order in which anet_traj_separation reads fastest"""
+    a, b = np.triu_indices(int(B), 1)
+    return np.stack([a, b], axis=1).astype(np.int32)
+
+
+def traj_separation(coeffs, T, pairs=None, t0=None, cutoff=np.inf, ctx=None):
+    """Exact minimum separation between pairs of trajectories of one batch (anet_traj_separation), metres: the minimum over the
+    time both trajectories of a pair exist of ||p_a(t) - p_b(t)||, found between the samples, not on them.
+    coeffs (B,N,3,D), T (B,N); t0 (B,): global start times (None: 0); pairs (P,2) int: indices into the batch (None: every a < b,
+    sorted by a).  Knots are the float64 sums t0 + T_0 + ... in piece order; a piece of zero duration occupies no time (padding).
+    cutoff: a separation at or above it need not be refined (it is still an actual distance of the two curves, never below the
+    exact minimum); inf: off.  Holding position before the start or after the end is not a mode: prepend or append a constant
+    piece of the wanted duration.
+    -> (sep (P,), t (P,) global time of a minimum, pieces (P,2) int32, pairs (P,2) int32).  No common time: (inf, 0, -1, -1); a
+    non-finite or negative duration, a non-finite t0, or a non-finite coefficient in a piece that is used: (nan, 0, -1, -1) for
+    that pair only.  An index outside [0, B) raises AnetError."""
+    ctx = ctx or default_context()
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.float64)
+    T = np.ascontiguousarray(T, dtype=np.float64)
+    B, N, three, D = coeffs.shape
+    if three != 3 or T.shape != (B, N) or D not in (4, 6, 8):
+        raise ValueError("shape mismatch")
+    if t0 is not None:
+        t0 = np.ascontiguousarray(t0, dtype=np.float64)
+        if t0.shape != (B,):
+            raise ValueError("t0: one start time per trajectory")
+    pairs = all_pairs(B) if pairs is None else np.asarray(pairs)
+    if pairs.ndim != 2 or pairs.shape[1] != 2 or not np.issubdtype(pairs.dtype, np.integer):
+        raise ValueError("pairs: (P, 2) integers")
+    if pairs.size and (pairs.min() < -2 ** 31 or pairs.max() >= 2 ** 31):
+        raise ValueError("pairs: indices must fit int32")
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+    P = pairs.shape[0]
+    pa, pb = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+    sep = np.empty(P)
+    t = np.empty(P)
+    qa, qb = np.empty(P, dtype=np.int32), np.empty(P, dtype=np.int32)
+    ctx.check(ctx.lib.anet_traj_separation(ctx.handle, D // 2, N, B, _ptr(coeffs), _ptr(T), None if t0 is None else _ptr(t0), P,
+                                           _ptr(pa), _ptr(pb), float(cutoff), _ptr(sep), _ptr(t), _ptr(qa), _ptr(qb)))
+    return sep, t, np.stack([qa, qb], axis=1), pairs
+
+
+def traj_separation_dev(coeffs, T, pair_a, pair_b, s, n_pieces, batch, t0=None, cutoff=np.inf, sep=None, t=None, piece_a=None,
+                        piece_b=None, ctx=None):
+    """anet_traj_separation_dev on CUDA tensors, asynchronous on torch's current stream: coeffs (N*3*2s, ld), T (N, ld) float64
+    batch-minor; t0 (>= batch,) float64 or None; pair_a, pair_b (P,) int32 -> (sep (P,) float64, t (P,) float64, piece_a (P,)
+    int32, piece_b (P,) int32).  Caller-supplied outputs may be longer than P: elements from P on are not touched.  t=False /
+    piece_a=False / piece_b=False: not wanted.  A pair with an index outside [0, batch) gets (nan, 0, -1, -1)."""
+    import torch
+    ctx = ctx or default_context()
+    ld = int(T.shape[1])
+    if coeffs.dtype != torch.float64 or T.dtype != torch.float64 or not (coeffs.is_contiguous() and T.is_contiguous()):
+        raise ValueError("traj_separation_dev: contiguous float64 tensors expected")
+    if tuple(coeffs.shape) != (n_pieces * 6 * s, ld) or T.shape[0] != n_pieces:
+        raise ValueError("shape mismatch")
+    if t0 is not None and (t0.dtype != torch.float64 or not t0.is_cuda or not t0.is_contiguous() or t0.dim() != 1 or t0.numel() < batch):
+        raise ValueError("traj_separation_dev: t0 is a contiguous float64 CUDA tensor, one per trajectory")
+    P = int(pair_a.numel())
+    for x in (pair_a, pair_b):
+        if x.dtype != torch.int32 or not x.is_cuda or not x.is_contiguous() or x.dim() != 1 or x.numel() != P:
+            raise ValueError("traj_separation_dev: pair_a, pair_b are contiguous int32 CUDA tensors of one length")
+    if sep is None:
+        sep = torch.empty(P, dtype=torch.float64, device=T.device)
+    if t is None:
+        t = torch.empty(P, dtype=torch.float64, device=T.device)
+    if piece_a is None:
+        piece_a = torch.empty(P, dtype=torch.int32, device=T.device)
+    if piece_b is None:
+        piece_b = torch.empty(P, dtype=torch.int32, device=T.device)
+    for out, dt in ((sep, torch.float64), (t, torch.float64), (piece_a, torch.int32), (piece_b, torch.int32)):
+        if out is not False and (out.dtype != dt or out.dim() != 1 or out.numel() < P or not out.is_contiguous() or not out.is_cuda):
+            raise ValueError("traj_separation_dev: outputs are contiguous CUDA vectors of at least P elements, float64 / int32")
+    if sep is False:
+        raise ValueError("traj_separation_dev: sep is always written")
+    p = lambda x: None if (x is None or x is False) else ctypes.c_void_p(x.data_ptr())
+    stream = ctypes.c_void_p(torch.cuda.current_stream(T.device).cuda_stream)
+    ctx.check(ctx.lib.anet_traj_separation_dev(ctx.handle, int(s), int(n_pieces), int(batch), ld, p(coeffs), p(T), p(t0), P, p(pair_a),
+                                               p(pair_b), float(cutoff), p(sep), p(t), p(piece_a), p(piece_b), stream))
+    return sep, (None if t is False else t), (None if piece_a is False else piece_a), (None if piece_b is False else piece_b)
+
+
+def separation_at_least(sep, min_dist):
+    """True when every separation is >= min_dist; a NaN is False; +inf (no common time) is clear"""
+    return bool(np.all(np.asarray(sep, dtype=np.float64) >= float(min_dist)))
+
+
 def piece_normalized_coeffs(coeffs, T, deriv, ctx=None):
     """Piece::normalizePosCoeffMat / normalizeVelCoeffMat / normalizeAccCoeffMat (trajectory.hpp:135-171) for a batch of pieces:
     coefficients of position (deriv 0), velocity (1) or acceleration (2) in normalised time.  coeffs (P,3,D), T (P,) -> (P,3,D-deriv)."""
@@ -541,6 +628,40 @@ class Trajectory:
     def checkClearance(self, points, min_dist):
         """True when every piece keeps at least min_dist metres from every point, exactly; a NaN clearance is False."""
         return clearance_at_least(self.getClearance(points, per_piece=True)[0], min_dist)
+
+    # --- exact minimum separation to another trajectory (no counterpart in the reference) ---------------------------------
+    def _pair_arrays(self, other):
+        """both trajectories as one batch of two: the shorter is padded with pieces of zero duration, which occupy no time"""
+        if not self.pieces or not other.pieces:
+            raise RuntimeError("empty trajectory")
+        D = self.pieces[0].coeffMat.shape[1]
+        if any(p.coeffMat.shape[1] != D for p in self.pieces + other.pieces):
+            raise ValueError("getSeparation: both trajectories must have one order")
+        N = max(len(self.pieces), len(other.pieces))
+        co = np.zeros((2, N, 3, D))
+        T = np.zeros((2, N))
+        for r, tr in enumerate((self, other)):
+            for i, p in enumerate(tr.pieces):
+                co[r, i] = p.coeffMat
+                T[r, i] = p.duration
+        return co, T
+
+    def getSeparation(self, other, t0=0.0, other_t0=0.0, cutoff=np.inf):
+        """(d, t, piece_self, piece_other): the exact smallest distance, in metres, between this trajectory started at global
+        time t0 and `other` started at other_t0, over the time both exist; the global time at which it is attained and the two
+        pieces.  (inf, 0, -1, -1): no common time.  Holding position before the start or after the end is not a mode: prepend
+        or append a constant piece (a coefficient matrix with only its last column set) of the wanted duration."""
+        co, T = self._pair_arrays(other)
+        sep, t, pieces, _ = traj_separation(co, T, np.array([[0, 1]], dtype=np.int32), np.array([float(t0), float(other_t0)]),
+                                            cutoff, ctx=self._ctx)
+        return float(sep[0]), float(t[0]), int(pieces[0, 0]), int(pieces[0, 1])
+
+    def checkSeparation(self, other, min_dist, t0=0.0, other_t0=0.0):
+        """True when the two trajectories keep at least min_dist metres apart over their common time, exactly; a NaN separation
+        is False, no common time is True.  Separations above min_dist are not refined (cutoff just above min_dist)."""
+        min_dist = float(min_dist)
+        cutoff = max(np.nextafter(min_dist, np.inf), 0.0)
+        return separation_at_least(self.getSeparation(other, t0, other_t0, cutoff)[0], min_dist)
 
     # --- the vehicle's own terms: thrust, attitude, body rate through the flatness map (flatness.py) ---------------
     def getFlatState(self, t, flatmap):

@@ -886,6 +886,36 @@ int anet_traj_clearance_dev(anet_ctx *ctx, int s, int n_pieces, int64_t batch, i
 int anet_traj_clearance(anet_ctx *ctx, int s, int n_pieces, int64_t batch, const double *coeffs, const double *T, int n_sets,
                         int64_t max_points, const double *points /* HOST */, const int32_t *counts /* HOST or NULL */,
                         double *clearance, int32_t *point, double *t);
+/* Exact minimum separation between pairs of trajectories of one batch (no counterpart in the reference): for the pair (a, b)
+ *     sep = min over the common intervals, min over t, of || p_a,i(t - K_i^a) - p_b,j(t - K_j^b) ||      (Euclidean, metres)
+ * Knots are float64 by definition: K_0 = t0 (t0 == NULL: 0), K_(i+1) = K_i + T_i summed in piece order; piece i lives on global time
+ * [K_i, K_(i+1)] and is evaluated at local time t - K_i; a piece with K_(i+1) == K_i occupies no time (T_i = 0: padding).  The window
+ * is W = [max(K_0^a, K_0^b), min(K_N^a, K_N^b)]; the intervals are the maximal sub-intervals of W of positive length between
+ * consecutive distinct knots of either trajectory, each closed and with its own two pieces at both ends (trajectories need not be
+ * continuous).  Not sampled: the minimum between two samples is found.  Holding position before the start or after the end is
+ * not a mode: prepend or append a constant piece.
+ * t (may be NULL): the global time of a minimum; piece_a, piece_b (may be NULL): its pieces.  They are diagnostics specified by
+ * consistency, as point and t of anet_traj_clearance are: the distance of the two named pieces at t reproduces sep within the
+ * bound, and t lies in W and in both pieces' spans; there is no tie-breaking rule.  No interval (disjoint or merely touching
+ * windows): sep +inf, t 0, pieces -1.  a == b is a valid pair with separation 0.  sep NaN, t 0, pieces -1, for that pair only: a
+ * duration, t0 or knot of either trajectory that is not finite, a negative duration; a coefficient or a product c_k T_i^k that is
+ * not finite in a piece that takes part in an interval (a piece that takes part in none is not read); on the _dev form a pair
+ * index outside [0, batch), for which nothing is read.  The host form refuses such an index with ANET_ERR_INVALID.
+ * cutoff >= 0 (INFINITY: off; NaN or negative: ANET_ERR_INVALID): every reported sep is an actual distance of the two curves at
+ * the reported t, with or without a cutoff; it is within the full bound of the exact minimum whenever that minimum is below
+ * cutoff; an interval whose certified lower bound is at least cutoff is left at its best sampled distance.
+ * coeffs, T: the layouts of anet_traj_clearance[_dev]; t0: [batch]; pair_a, pair_b: int32 [n_pairs]; sep, t, piece_a, piece_b:
+ * [n_pairs]; everything on the device for the _dev form and on the host for the host form.  n_pairs == 0 or batch == 0 returns
+ * ANET_OK after the argument checks and touches nothing.  No workspace.  A pair list sorted by a reads fastest.
+ * Accuracy (csrc/separation_kernels.h): |sep - exact| <= 64 eps scale + 4 eps |t| v + location term, scale the two pieces' sums of
+ * |c_k T^k|, v a bound of the two speeds, |t| the largest modulus of the times involved; never below the exact minimum by more
+ * than the first two terms. */
+int anet_traj_separation_dev(anet_ctx *ctx, int s, int n_pieces, int64_t batch, int64_t ld, const double *coeffs, const double *T,
+                             const double *t0 /* [batch] or NULL */, int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b,
+                             double cutoff, double *sep, double *t, int32_t *piece_a, int32_t *piece_b, void *stream);
+int anet_traj_separation(anet_ctx *ctx, int s, int n_pieces, int64_t batch, const double *coeffs, const double *T,
+                         const double *t0 /* [batch] or NULL */, int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b,
+                         double cutoff, double *sep, double *t, int32_t *piece_a, int32_t *piece_b);
 
 /* ---- front-end route on the voxel map: sfc_gen::planPath ----------------------------------------------------------------
  * A collision-free polyline from s to g and its length, by a shortest-path field on the grid, a walk back along it and a
