@@ -64,13 +64,7 @@ int anet_traj_clearance(anet_ctx *ctx, int s, int n_pieces, int64_t batch, const
   if (rc) return rc;
   if ((rc = st.download(d_c, n_pieces, clearance))) return rc;
   if (t && (rc = st.download(d_t, n_pieces, t))) return rc;
-  if (point) {  // the int32 plane comes back as it lies, [N][ld], and is turned on the host
-    std::vector<int32_t> h((size_t)n_pieces * st.ld);
-    ANET_HIP(ctx, hipMemcpyAsync(h.data(), d_point, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
-    ANET_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int64_t bb = 0; bb < batch; ++bb)
-      for (int i = 0; i < n_pieces; ++i) point[bb * n_pieces + i] = h[(size_t)i * st.ld + bb];
-  }
+  if (point && (rc = st.download_rows(d_point, n_pieces, point))) return rc;
   return ANET_OK;
 }
 

@@ -256,6 +256,18 @@ struct HipStaging {
 };
 struct Stager : anet::Staging<HipStaging> {
   Stager(anet_ctx *ctx, int64_t batch) : Staging{{ctx}, batch, batch == 1 ? 1 : anet_recommended_ld(batch)} {}
+  // an int32 row plane [n][ld] on the device (Pass::rows) -> host [batch][n]: the plane comes back as it lies and is turned on
+  // the host; the stream is idle on return
+  int download_rows(const int32_t *dev, int64_t n, int32_t *host) {
+    std::vector<int32_t> h((size_t)(n * ld));
+    hipError_t e = hipMemcpyAsync(h.data(), dev, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, tr.ctx->stream);
+    if (e != hipSuccess) return hip_fail(tr.ctx, e, "hipMemcpyAsync(D2H)");
+    e = hipStreamSynchronize(tr.ctx->stream);
+    if (e != hipSuccess) return hip_fail(tr.ctx, e, "hipStreamSynchronize");
+    for (int64_t bb = 0; bb < batch; ++bb)
+      for (int64_t i = 0; i < n; ++i) host[bb * n + i] = h[(size_t)(i * ld + bb)];
+    return ANET_OK;
+  }
 };
 
 // the parameter check of every L-BFGS entry point

@@ -56,13 +56,7 @@ int anet_traj_row_margin(anet_ctx *ctx, int s, int n_pieces, int64_t batch, cons
   if (rc) return rc;
   if ((rc = st.download(d_m, n_pieces, margin))) return rc;
   if (t && (rc = st.download(d_t, n_pieces, t))) return rc;
-  if (row) {  // int32 rows come back as they lie, [N][ld], and are turned on the host
-    std::vector<int32_t> h((size_t)n_pieces * st.ld);
-    ANET_HIP(ctx, hipMemcpyAsync(h.data(), d_row, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
-    ANET_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int64_t bb = 0; bb < batch; ++bb)
-      for (int i = 0; i < n_pieces; ++i) row[bb * n_pieces + i] = h[(size_t)i * st.ld + bb];
-  }
+  if (row && (rc = st.download_rows(d_row, n_pieces, row))) return rc;
   return ANET_OK;
 }
 

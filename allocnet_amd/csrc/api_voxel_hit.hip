@@ -53,13 +53,7 @@ int anet_traj_voxel_hit(anet_ctx *ctx, int s, int n_pieces, int64_t batch, const
   rc = anet_traj_voxel_hit_dev(ctx, s, n_pieces, batch, st.ld, d_co, d_T, grid, voxels, d_t, voxel ? d_vox : nullptr, ctx->stream);
   if (rc) return rc;
   if ((rc = st.download(d_t, n_pieces, t_hit))) return rc;
-  if (voxel) {  // the int32 plane comes back as it lies, [N][ld], and is turned on the host
-    std::vector<int32_t> h((size_t)n_pieces * st.ld);
-    ANET_HIP(ctx, hipMemcpyAsync(h.data(), d_vox, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
-    ANET_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int64_t bb = 0; bb < batch; ++bb)
-      for (int i = 0; i < n_pieces; ++i) voxel[bb * n_pieces + i] = h[(size_t)i * st.ld + bb];
-  }
+  if (voxel && (rc = st.download_rows(d_vox, n_pieces, voxel))) return rc;
   return ANET_OK;
 }
 

@@ -28,13 +28,12 @@
 // SURVIVORS.  The critical points of g(tau) = || u(tau) - q ||^2 are the roots of h = g' / 2 = (u - q) . u'.  The control values
 // of h / n (degree 2n - 1) are formed ONCE per survivor from the Bernstein forms of u - q and u' -- a product of Bernstein
 // polynomials is a sum of positive weights times control-value products, so nothing is expanded into monomials and nothing
-// cancels that does not cancel in h itself.  Their sign changes bound the roots of h in an interval (variation diminishing);
-// intervals are halved by de Casteljau until one holds at most one sign change.  No change: dropped (its ends are candidates
-// already).  One change, + to -: a maximum, dropped.  One change, - to +: bisected (kClrBisect halvings at most, until the ends
-// are neighbouring doubles) on h evaluated from the three component polynomials, Horner per axis for u and u' together -- never
-// from coefficients of g.  More than one: the midpoint is a candidate and the interval is split, down to 2^-kClrMaxDepth, where
-// the midpoint stands for the cluster.  An interval over which g varies by less than (eps scale_j)^2 yields its midpoint.  The
-// intervals are dyadic and visited without a stack, as in corridor_margin_kernels.h: (level, index) is rebuilt from the root.
+// cancels that does not cancel in h itself (bern::product_cv).  The roots of h are isolated by the walk of bernstein_walk.h
+// (kClrMaxDepth, kClrMaxNodes visits per survivor).  No sign change: dropped (its ends are candidates already).  One change, + to
+// -: a maximum, dropped.  One change, - to +: bisected (kClrBisect halvings at most, until the ends are neighbouring doubles) on
+// h evaluated from the three component polynomials, Horner per axis for u and u' together -- never from coefficients of g.
+// More than one: the midpoint is a candidate and the interval is split; at the depth bound the midpoint stands for the
+// cluster.  An interval over which g varies by less than (eps scale_j)^2 yields its midpoint.
 // Every candidate's VALUE is the norm of the difference vector at the candidate time, from the components: an actual distance of
 // the curve, never below the true minimum by more than its own rounding.
 // BUDGETS.  Loops: tiles ceil(count / 64), twice; points per tile 64; marked points per tile 64; interval visits per survivor
@@ -50,6 +49,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include "bernstein_walk.h"
 
 namespace anet {
 
@@ -71,12 +71,6 @@ constexpr int kClrBisect = 64;
 constexpr double kClrEps = 2.220446049250313e-16;
 constexpr double kClrSlack = 16.0;   // in eps * scale_j, see CHEAP PART
 
-constexpr double clr_binom(int n, int k) {
-  double r = 1.0;
-  for (int j = 0; j < k; ++j) r = r * (double)(n - j) / (double)(j + 1);
-  return r;
-}
-
 template <int S>
 __global__ void __launch_bounds__(64) k_traj_clearance(ClearanceArgs a) {
   constexpr int D = 2 * S, n = D - 1;  // D control values per axis, degree n
@@ -92,24 +86,8 @@ __global__ void __launch_bounds__(64) k_traj_clearance(ClearanceArgs a) {
   const double Ti = a.T[o];
   bool bad = !(fabs(Ti) < INFINITY) || Ti < 0.0;
   // u[ax][k]: ascending coefficients of p(T tau)
-  double u[3][D], A1 = 0.0;
-  {
-    double tk[D];
-    tk[0] = 1.0;
-#pragma unroll
-    for (int k = 1; k < D; ++k) tk[k] = tk[k - 1] * Ti;
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-#pragma unroll
-      for (int k = 0; k < D; ++k) {
-        const double c = a.coeffs[(int64_t)((i * 3 + ax) * D + (n - k)) * ld + b];
-        bad = bad || !(fabs(c) < INFINITY);
-        u[ax][k] = c * tk[k];
-        bad = bad || !(fabs(u[ax][k]) < INFINITY);
-        A1 += fabs(u[ax][k]);
-      }
-    }
-  }
+  double u[3][D], A1;
+  bad = !bern::normalised<D>(a.coeffs, i, b, ld, Ti, u, A1) || bad;
   if (bad) {  // the lane goes on with a harmless curve: it still serves the tile loads and the barriers
 #pragma unroll
     for (int ax = 0; ax < 3; ++ax)
@@ -121,29 +99,11 @@ __global__ void __launch_bounds__(64) k_traj_clearance(ClearanceArgs a) {
   double bz[3][D], pos[3][kClrK];
 #pragma unroll
   for (int ax = 0; ax < 3; ++ax) {
+    bern::to_bernstein<D>(u[ax], bz[ax]);
 #pragma unroll
-    for (int ii = 0; ii < D; ++ii) {
-      double acc = u[ax][0];
-#pragma unroll
-      for (int k = 1; k <= ii; ++k) acc = __builtin_fma(clr_binom(ii, k) / clr_binom(n, k), u[ax][k], acc);
-      bz[ax][ii] = acc;
-    }
-#pragma unroll
-    for (int k = 0; k < kClrK; ++k) {
-      const double tau = (double)k / (double)(kClrK - 1);
-      double v = u[ax][n];
-#pragma unroll
-      for (int p = n - 1; p >= 0; --p) v = __builtin_fma(v, tau, u[ax][p]);
-      pos[ax][k] = v;
-    }
+    for (int k = 0; k < kClrK; ++k) pos[ax][k] = bern::horner<D>(u[ax], (double)k / (double)(kClrK - 1));
   }
-  double Lh2 = 0.0;
-#pragma unroll
-  for (int k = 0; k < n; ++k) {
-    const double dx = bz[0][k + 1] - bz[0][k], dy = bz[1][k + 1] - bz[1][k], dz = bz[2][k + 1] - bz[2][k];
-    Lh2 = fmax(Lh2, __builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)));
-  }
-  Lh2 = sqrt(Lh2) * ((double)n * 0.5 / (double)(kClrK - 1));
+  const double Lh2 = bern::lipschitz_half_step<n>(bz, kClrK);
 
   const int set = a.per_piece ? i : 0;
   int64_t cnt = a.max_points;
@@ -224,64 +184,26 @@ __global__ void __launch_bounds__(64) k_traj_clearance(ClearanceArgs a) {
       const double flat = (kClrEps * sc) * (kClrEps * sc);
       // a candidate: the distance from the three components at tau
       auto candidate = [&](double tau) {
-        double d2 = 0.0;
+        double v[3], d2 = 0.0;
+        bern::horner3<D>(u, tau, v);
 #pragma unroll
-        for (int ax = 0; ax < 3; ++ax) {
-          double v = u[ax][n];
-#pragma unroll
-          for (int k = n - 1; k >= 0; --k) v = __builtin_fma(v, tau, u[ax][k]);
-          v -= q[ax];
-          d2 = __builtin_fma(v, v, d2);
-        }
+        for (int ax = 0; ax < 3; ++ax) d2 = __builtin_fma(v[ax] - q[ax], v[ax] - q[ax], d2);
         if (d2 < best2) { best2 = d2; bestd = sqrt(d2); bp = (int)(base + jj); bt = tau; }
       };
       // control values of h / n = (u - q) . u' / n on [0, 1]
-      double dv[M];
+      double x[3][D], dv[M];
 #pragma unroll
-      for (int k = 0; k < M; ++k) dv[k] = 0.0;
+      for (int ax = 0; ax < 3; ++ax)
 #pragma unroll
-      for (int ii = 0; ii <= n; ++ii) {
-#pragma unroll
-        for (int j = 0; j < n; ++j) {
-          double dot = 0.0;
-#pragma unroll
-          for (int ax = 0; ax < 3; ++ax) dot = __builtin_fma(bz[ax][ii] - q[ax], bz[ax][j + 1] - bz[ax][j], dot);
-          dv[ii + j] = __builtin_fma(clr_binom(n, ii) * clr_binom(n - 1, j) / clr_binom(2 * n - 1, ii + j), dot, dv[ii + j]);
-        }
-      }
-      int lev = 0;
-      uint32_t idx = 0;
+        for (int k = 0; k < D; ++k) x[ax][k] = bz[ax][k] - q[ax];
+      bern::product_cv<n>(x, bz, dv);
+      bern::Dyadic<kClrMaxDepth, uint32_t> walk;
       for (int guard = 0; guard < kClrMaxNodes; ++guard) {
-        // the interval (lev, idx) = [idx, idx + 1] / 2^lev from the root; in place, w ends as the right half
         double w[M];
-#pragma unroll
-        for (int k = 0; k < M; ++k) w[k] = dv[k];
-        for (int l = 0; l < lev && l < kClrMaxDepth; ++l) {
-          const bool right = (idx >> (lev - 1 - l)) & 1u;
-          double le[M];
-          le[0] = w[0];
-#pragma unroll
-          for (int r = 1; r < M; ++r) {
-#pragma unroll
-            for (int k = 0; k < M - r; ++k) w[k] = 0.5 * (w[k] + w[k + 1]);
-            le[r] = w[0];
-          }
-#pragma unroll
-          for (int k = 0; k < M; ++k) w[k] = right ? w[k] : le[k];
-        }
-        int var = 0, last = 0, first = 0;
-        double mx = 0.0;
-#pragma unroll
-        for (int k = 0; k < M; ++k) {
-          const int sg = (w[k] > 0.0) - (w[k] < 0.0);
-          mx = fmax(mx, fabs(w[k]));
-          if (sg != 0) {
-            if (first == 0) first = sg;
-            if (last != 0 && sg != last) ++var;
-            last = sg;
-          }
-        }
-        const double width = ldexp(1.0, -lev), lo = (double)idx * width, mid = lo + 0.5 * width;
+        walk.descend<M>(dv, w);
+        const bern::Signs sg = bern::signs<M>(w);
+        const int var = sg.var, first = sg.first;
+        const double mx = sg.mx, width = walk.width(), lo = walk.lo(), mid = lo + 0.5 * width;
         bool split = false;
         if (var == 0) {
           // monotone: its ends are split points or 0, 1
@@ -311,16 +233,9 @@ __global__ void __launch_bounds__(64) k_traj_clearance(ClearanceArgs a) {
           }
         } else {
           candidate(mid);  // the split point, or the cluster's location at the depth bound
-          split = lev < kClrMaxDepth;
+          split = walk.can_split();
         }
-        if (split) {
-          ++lev;
-          idx <<= 1;
-        } else {
-          for (int c = 0; c < kClrMaxDepth && lev > 0 && (idx & 1u); ++c) { idx >>= 1; --lev; }
-          if (lev == 0) break;
-          idx += 1;
-        }
+        if (!walk.advance(split)) break;
       }
     }
   }

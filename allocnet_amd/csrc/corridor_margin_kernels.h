@@ -30,18 +30,13 @@
 // three FMAs and subtraction add 4 (one fewer on any one term): 12 roundings of relative size eps / 2 = 6 eps scale_r, rounded up
 // to 8.  So a pruned row has max g_r <= best in exact arithmetic on the lane's u: pruning changes the result by nothing beyond
 // the error `best` itself carries.
-// SURVIVING ROWS.  The control values of g_r' are the differences of those of g_r.  Their sign changes bound the roots of g_r' in
-// an interval (variation diminishing); intervals are halved by de Casteljau until one holds at most one sign change.  An interval
-// whose first sign is negative holds a minimum and is dropped; one with a single + to - change is bisected (48 halvings on the
+// SURVIVING ROWS.  The control values of g_r' are the differences of those of g_r; the roots of g_r' are isolated by the walk of
+// bernstein_walk.h (kMarginMaxDepth, kMarginMaxNodes visits per row).  A visit without a sign change is dropped; one whose first
+// sign is negative holds a minimum and is dropped; one with a single + to - change is bisected (kMarginBisect halvings on the
 // monomial g_r', which only LOCATES the candidate).  An interval over which g_r varies by less than eps scale_r (width times the
-// largest derivative control value) yields its midpoint; so does one at the depth bound 2^-20 (a cluster of critical points:
-// g_r varies there by the cube of the width).  Every split point is a candidate as well, so a critical point that falls exactly
-// on one is not lost between two intervals that each see no sign change.
-// The intervals are dyadic and visited without a stack: the interval (level, index) is rebuilt from the root by `level` splits
-// chosen by the bits of the index.  That costs `level` splits per visit instead of one, on the few rows that survive and at the
-// depth 2 or 3 that separated roots need, and keeps the lane free of private memory (the 24 x (MAXN + 1) doubles of
-// k_piece_max_rate's stack are scratch): no scratch, no LDS.  Loops: rows M, three times; visits kMarginMaxNodes; splits per visit and the
-// climb to the next interval kMarginMaxDepth; bisection kMarginBisect -- all structural, no input can spin a wave.
+// largest derivative control value) yields its midpoint; so does one at the depth bound (a cluster of critical points: g_r
+// varies there by the cube of the width).  Every split point is a candidate.  Loops: rows M, three times; the walk's own;
+// bisection kMarginBisect -- all structural.  No scratch, no LDS.
 // CANDIDATE VALUES are always taken from the three component polynomials, Horner per axis, then the dot product with a_r, minus
 // b_r -- never from the monomial coefficients of g_r (rate_kernels.h explains what that costs on Chebyshev-like pieces).
 // TOLERANCE.  |margin - exact| <= 32 eps (sum_ax |a_ax| sum_k |u_ax,k| + |b|), the largest over the piece's rows; derived in
@@ -51,6 +46,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include "bernstein_walk.h"
 
 namespace anet {
 
@@ -68,12 +64,6 @@ constexpr int kMarginMaxNodes = 1024;  // intervals visited per row at most
 constexpr int kMarginBisect = 48;
 constexpr double kMarginEps = 2.220446049250313e-16;
 constexpr double kMarginSlack = 8.0;   // in eps * scale_r, see PRUNING
-
-constexpr double margin_binom(int n, int k) {
-  double r = 1.0;
-  for (int j = 0; j < k; ++j) r = r * (double)(n - j) / (double)(j + 1);
-  return r;
-}
 
 template <int S>
 __global__ void __launch_bounds__(64) k_traj_row_margin(MarginArgs a) {
@@ -127,13 +117,7 @@ __global__ void __launch_bounds__(64) k_traj_row_margin(MarginArgs a) {
     }
     p1[ax] = s1;
     A[ax] = sa;
-#pragma unroll
-    for (int ii = 0; ii < D; ++ii) {
-      double acc = u[ax][0];
-#pragma unroll
-      for (int k = 1; k <= ii; ++k) acc = __builtin_fma(margin_binom(ii, k) / margin_binom(n, k), u[ax][k], acc);
-      bz[ax][ii] = acc;
-    }
+    bern::to_bernstein<D>(u[ax], bz[ax]);
   }
   double best = -INFINITY, bt = 0.0;
   int brow = -1;
@@ -176,12 +160,7 @@ __global__ void __launch_bounds__(64) k_traj_row_margin(MarginArgs a) {
     // a candidate: the value from the three components
     auto candidate = [&](double tau) {
       double v[3];
-#pragma unroll
-      for (int ax = 0; ax < 3; ++ax) {
-        v[ax] = u[ax][n];
-#pragma unroll
-        for (int k = n - 1; k >= 0; --k) v[ax] = __builtin_fma(v[ax], tau, u[ax][k]);
-      }
+      bern::horner3<D>(u, tau, v);
       const double g = dotrow(v[0], v[1], v[2]);
       if (g > best) { best = g; brow = r; bt = tau; }
     };
@@ -200,41 +179,13 @@ __global__ void __launch_bounds__(64) k_traj_row_margin(MarginArgs a) {
       dv[k] = cv[k + 1] - cv[k];
       gd[k] = (double)(k + 1) * __builtin_fma(rc, u[2][k + 1], __builtin_fma(rb, u[1][k + 1], ra * u[0][k + 1]));
     }
-    int lev = 0;
-    uint32_t idx = 0;
+    bern::Dyadic<kMarginMaxDepth, uint32_t> walk;
     for (int guard = 0; guard < kMarginMaxNodes; ++guard) {
-      // the interval (lev, idx) = [idx, idx + 1] / 2^lev from the root
       double w[n];
-#pragma unroll
-      for (int k = 0; k < n; ++k) w[k] = dv[k];
-      for (int l = 0; l < lev && l < kMarginMaxDepth; ++l) {
-        const bool right = (idx >> (lev - 1 - l)) & 1u;
-        double le[n], ri[n];
-        le[0] = w[0];
-        ri[n - 1] = w[n - 1];
-#pragma unroll
-        for (int q = 1; q < n; ++q) {
-#pragma unroll
-          for (int k = 0; k < n - q; ++k) w[k] = 0.5 * (w[k] + w[k + 1]);
-          le[q] = w[0];
-          ri[n - 1 - q] = w[n - 1 - q];
-        }
-#pragma unroll
-        for (int k = 0; k < n; ++k) w[k] = right ? ri[k] : le[k];
-      }
-      int var = 0, last = 0, first = 0;
-      double mx = 0.0;
-#pragma unroll
-      for (int k = 0; k < n; ++k) {
-        const int sg = (w[k] > 0.0) - (w[k] < 0.0);
-        mx = fmax(mx, fabs(w[k]));
-        if (sg != 0) {
-          if (first == 0) first = sg;
-          if (last != 0 && sg != last) ++var;
-          last = sg;
-        }
-      }
-      const double width = ldexp(1.0, -lev), lo = (double)idx * width, mid = lo + 0.5 * width;
+      walk.descend<n>(dv, w);
+      const bern::Signs sg = bern::signs<n>(w);
+      const int var = sg.var, first = sg.first;
+      const double mx = sg.mx, width = walk.width(), lo = walk.lo(), mid = lo + 0.5 * width;
       bool split = false;
       if (var == 0) {
         // monotone: its ends are split points or 0, 1
@@ -245,25 +196,15 @@ __global__ void __launch_bounds__(64) k_traj_row_margin(MarginArgs a) {
           double l = lo, h = lo + width;
           for (int it = 0; it < kMarginBisect; ++it) {
             const double m = 0.5 * (l + h);
-            double fm = gd[n - 1];
-#pragma unroll
-            for (int k = n - 2; k >= 0; --k) fm = __builtin_fma(fm, m, gd[k]);
-            if (fm > 0.0) l = m; else h = m;
+            if (bern::horner<n>(gd, m) > 0.0) l = m; else h = m;
           }
           candidate(0.5 * (l + h));
         }
       } else {
         candidate(mid);  // the split point, or the cluster's location at the depth bound
-        split = lev < kMarginMaxDepth;
+        split = walk.can_split();
       }
-      if (split) {
-        ++lev;
-        idx <<= 1;
-      } else {
-        for (int q = 0; q < kMarginMaxDepth && lev > 0 && (idx & 1u); ++q) { idx >>= 1; --lev; }
-        if (lev == 0) break;
-        idx += 1;
-      }
+      if (!walk.advance(split)) break;
     }
   }
   a.margin[o] = bad ? NAN : best;

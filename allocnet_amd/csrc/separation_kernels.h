@@ -30,21 +30,19 @@
 // an index has advanced since the last interval.  `best` stays in the lane across the intervals: pruning across intervals, no
 // atomics, no workspace, and the same bits for a pair whatever else is in the launch and whatever ld is.
 // PER INTERVAL.  (1) A piece is held as the Bernstein control values of p(T tau) on [0, 1] (u_k = c_k T^k, then positive weights
-// C(i,k)/C(n,k), as k_traj_clearance does), formed when the piece is loaded.  (2) Each is restricted to the common interval
+// C(i,k)/C(n,k): bern::normalised and bern::to_bernstein), formed when the piece is loaded.  (2) Each is restricted to the common interval
 // [alpha, beta] = [(lo - K_i) / T_i, (hi - K_i) / T_i] by two de Casteljau subdivisions (left part at beta, right part at alpha /
 // beta): convex combinations of control values, no Taylor shift in monomials.  (3) d = a - b, control value by control value: the
 // difference curve in sigma in [0, 1], t = lo + sigma (hi - lo).  (4) CHEAP PART: d at the kSepK = 9 values sigma_k = k / 8 (de
 // Casteljau); the smallest squared norm ub is a candidate (an actual distance), and lb = ub - L h / 2, L = n max_k ||d_(k+1) - d_k||
 // >= max ||d'||, h / 2 = 1 / 16, bounds the interval from below.  The interval is refined only when
 //     ub < min(best, cutoff) + L h / 2 + kSepSlack eps scale,        scale = sum |u^a| + sum |u^b|
-// (in squares, the right side rounded up).  (5) SURVIVORS: the procedure of clearance_kernels.h with the point at the origin,
-// restated: control values of h / n = d . d' / n (degree 2n - 1) from the Bernstein forms with positive weights; their sign
-// changes bound the roots (variation diminishing); dyadic halving by de Casteljau until an interval holds at most one; none:
+// (in squares, the right side rounded up).  (5) SURVIVORS: the rule of clearance_kernels.h with the point at the origin, on the
+// walk of bernstein_walk.h (kSepMaxDepth, kSepMaxNodes): control values of h / n = d . d' / n (bern::product_cv); no sign change:
 // dropped; one, + to -: a maximum, dropped; one, - to +: bisected (kSepBisect halvings at most, to neighbouring doubles) on h
 // evaluated from the three components of d by de Casteljau, both ends candidates; more: the midpoint is a candidate and the
-// interval is split, down to 2^-kSepMaxDepth.  An interval over which g = ||d||^2 varies by less than (eps scale)^2 yields its
-// midpoint.  (level, index) is rebuilt from the root: no stack.  Every candidate's VALUE is the norm of the difference vector d
-// at the candidate sigma.
+// interval is split.  An interval over which g = ||d||^2 varies by less than (eps scale)^2 yields its midpoint.  Every
+// candidate's VALUE is the norm of the difference vector d at the candidate sigma.
 // BUDGETS.  Steps of the merge kSepMaxSteps (every step advances an index or the interval: 4N - 1 at most); intervals visited per
 // interval of time kSepMaxNodes; splits and the climb kSepMaxDepth; bisection kSepBisect -- structural, no input can spin a
 // wave.  When a budget runs out what has been found stands: a valid upper bound.
@@ -55,6 +53,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include "bernstein_walk.h"
 
 namespace anet {
 
@@ -78,40 +77,13 @@ constexpr int kSepBisect = 64;
 constexpr double kSepEps = 2.220446049250313e-16;
 constexpr double kSepSlack = 64.0;   // in eps * scale, see PER INTERVAL (4)
 
-constexpr double sep_binom(int n, int k) {
-  double r = 1.0;
-  for (int j = 0; j < k; ++j) r = r * (double)(n - j) / (double)(j + 1);
-  return r;
-}
-
 // piece i of trajectory b -> Bernstein control values of p(T tau) on [0, 1], the coefficient-modulus sum; false: not finite
 template <int S>
 __device__ __forceinline__ bool sep_load(const SeparationArgs &a, int i, int64_t b, double Ti, double (&z)[3][2 * S], double &A) {
-  constexpr int D = 2 * S, n = D - 1;
-  bool ok = true;
-  double tk[D];
-  tk[0] = 1.0;
+  double u[3][2 * S];
+  const bool ok = bern::normalised<2 * S>(a.coeffs, i, b, a.ld, Ti, u, A);
 #pragma unroll
-  for (int k = 1; k < D; ++k) tk[k] = tk[k - 1] * Ti;
-  A = 0.0;
-#pragma unroll
-  for (int ax = 0; ax < 3; ++ax) {
-    double u[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      const double c = a.coeffs[(int64_t)((i * 3 + ax) * D + (n - k)) * a.ld + b];
-      u[k] = c * tk[k];
-      ok = ok && fabs(c) < INFINITY && fabs(u[k]) < INFINITY;
-      A += fabs(u[k]);
-    }
-#pragma unroll
-    for (int ii = 0; ii < D; ++ii) {
-      double acc = u[0];
-#pragma unroll
-      for (int k = 1; k <= ii; ++k) acc = __builtin_fma(sep_binom(ii, k) / sep_binom(n, k), u[k], acc);
-      z[ax][ii] = acc;
-    }
-  }
+  for (int ax = 0; ax < 3; ++ax) bern::to_bernstein<2 * S>(u[ax], z[ax]);
   return ok;
 }
 
@@ -224,63 +196,20 @@ __global__ void __launch_bounds__(64) k_traj_separation(SeparationArgs a) {
       // cheap part
       double ub2 = INFINITY;
       for (int k = 0; k < kSepK; ++k) ub2 = fmin(ub2, candidate((double)k / (double)(kSepK - 1)));
-      double Lh2 = 0.0;
-#pragma unroll
-      for (int k = 0; k < n; ++k) {
-        const double dx = d[0][k + 1] - d[0][k], dy = d[1][k + 1] - d[1][k], dz = d[2][k + 1] - d[2][k];
-        Lh2 = fmax(Lh2, __builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)));
-      }
-      Lh2 = sqrt(Lh2) * ((double)n * 0.5 / (double)(kSepK - 1));
+      const double Lh2 = bern::lipschitz_half_step<n>(d, kSepK);
       const double thr = fmin(bestd, a.cutoff) + Lh2 + kSepSlack * kSepEps * sc;
       if (ub2 < thr * thr * (1.0 + 8.0 * kSepEps)) {
         const double flat = (kSepEps * sc) * (kSepEps * sc);
         // control values of h / n = d . d' / n on [0, 1]
         double dv[M];
-#pragma unroll
-        for (int k = 0; k < M; ++k) dv[k] = 0.0;
-#pragma unroll
-        for (int ii = 0; ii <= n; ++ii) {
-#pragma unroll
-          for (int j = 0; j < n; ++j) {
-            double dot = 0.0;
-#pragma unroll
-            for (int ax = 0; ax < 3; ++ax) dot = __builtin_fma(d[ax][ii], d[ax][j + 1] - d[ax][j], dot);
-            dv[ii + j] = __builtin_fma(sep_binom(n, ii) * sep_binom(n - 1, j) / sep_binom(2 * n - 1, ii + j), dot, dv[ii + j]);
-          }
-        }
-        int lev = 0;
-        uint32_t idx = 0;
+        bern::product_cv<n>(d, d, dv);
+        bern::Dyadic<kSepMaxDepth, uint32_t> walk;
         for (int guard = 0; guard < kSepMaxNodes; ++guard) {
-          // the interval (lev, idx) = [idx, idx + 1] / 2^lev from the root; in place, w ends as the right half
           double w[M];
-#pragma unroll
-          for (int k = 0; k < M; ++k) w[k] = dv[k];
-          for (int l = 0; l < lev && l < kSepMaxDepth; ++l) {
-            const bool right = (idx >> (lev - 1 - l)) & 1u;
-            double le[M];
-            le[0] = w[0];
-#pragma unroll
-            for (int r = 1; r < M; ++r) {
-#pragma unroll
-              for (int k = 0; k < M - r; ++k) w[k] = 0.5 * (w[k] + w[k + 1]);
-              le[r] = w[0];
-            }
-#pragma unroll
-            for (int k = 0; k < M; ++k) w[k] = right ? w[k] : le[k];
-          }
-          int var = 0, last = 0, first = 0;
-          double mx = 0.0;
-#pragma unroll
-          for (int k = 0; k < M; ++k) {
-            const int sg = (w[k] > 0.0) - (w[k] < 0.0);
-            mx = fmax(mx, fabs(w[k]));
-            if (sg != 0) {
-              if (first == 0) first = sg;
-              if (last != 0 && sg != last) ++var;
-              last = sg;
-            }
-          }
-          const double width = ldexp(1.0, -lev), l0 = (double)idx * width, mid = l0 + 0.5 * width;
+          walk.descend<M>(dv, w);
+          const bern::Signs sn = bern::signs<M>(w);
+          const int var = sn.var, first = sn.first;
+          const double mx = sn.mx, width = walk.width(), l0 = walk.lo(), mid = l0 + 0.5 * width;
           bool split = false;
           if (var == 0) {
             // monotone: its ends are split points or 0, 1
@@ -312,16 +241,9 @@ __global__ void __launch_bounds__(64) k_traj_separation(SeparationArgs a) {
             }
           } else {
             candidate(mid);  // the split point, or the cluster's location at the depth bound
-            split = lev < kSepMaxDepth;
+            split = walk.can_split();
           }
-          if (split) {
-            ++lev;
-            idx <<= 1;
-          } else {
-            for (int c = 0; c < kSepMaxDepth && lev > 0 && (idx & 1u); ++c) { idx >>= 1; --lev; }
-            if (lev == 0) break;
-            idx += 1;
-          }
+          if (!walk.advance(split)) break;
         }
       }
       lo = hi;

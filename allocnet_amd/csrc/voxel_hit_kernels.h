@@ -21,8 +21,9 @@
 // PROCEDURE.  One lane per (trajectory, piece), blockIdx.y = piece: every coefficient load of a wave is one contiguous row
 // segment.  The lane forms q_ax in normalised time once, qu[ax][k] = c_k T^k / scale (k = 0: (c_0 - origin) / scale), converts
 // the three components to Bernstein form (3 x 2S control values) and keeps both in registers.  It then visits dyadic
-// sub-intervals [idx, idx + 1] / 2^lev of [0, 1] left first and without a stack (the (level, index) state of
-// k_traj_row_margin).  A visit blossoms the control values straight to [a, b] -- de Casteljau at b, then at a / b on the left
+// sub-intervals [idx, idx + 1] / 2^lev of [0, 1] left first and without a stack (the walk of bernstein_walk.h, with a 64-bit
+// index for the depth 32.  The (lev, idx) state is written out here: through bern::Dyadic the kernel measured 0.8 % slower at
+// 131 072 trajectories; the midpoint halving is not used here either).  A visit blossoms the control values straight to [a, b] -- de Casteljau at b, then at a / b on the left
 // part -- so it costs O(S^2) whatever its depth, and reduces each axis to its smallest and largest control value (the curve's
 // box on [a, b]), its two end values and whether its control values rise or fall strictly (the component is monotone).  Then:
 //   * the box covers at most kHitBoxCells cells: they are looked up.  None blocked and none outside: the interval is FREE.
@@ -43,7 +44,7 @@
 // whatever else is in the batch.  If the budget of visits runs out the answer is the conservative one described above.
 // COST.  Voxel reads are byte gathers through a const __restrict__ pointer; a planner map (200 x 200 x 40 = 1.6 MB) stays in L2.
 // A free piece is halved until each part's box is at most kHitBoxCells cells; the inner visits make no lookup.  Counted with the
-// float64 restatement of tests/test_traj_voxel_hit_cpu.py on 300 free jerk and 300 free snap pieces of 1 to 4 m in 0.25 m voxels:
+// float64 restatement tests/traj_voxel_hit_mp.hit_float64 on 300 free jerk and 300 free snap pieces of 1 to 4 m in 0.25 m voxels:
 // 13 visits and 36 byte lookups in the median, 21 visits and 56 lookups at the 90th percentile, 29 and 80 at most.
 //
 // ACCURACY.  t* the exact infimum, ax the axis whose plane is crossed there, u_ax,k the coefficients of q_ax in normalised time:
@@ -64,6 +65,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include "bernstein_walk.h"
 
 namespace anet {
 
@@ -85,12 +87,6 @@ constexpr int kHitBoxCells = 8;      // a box of more cells is split, not looked
 constexpr double kHitC = 32.0;       // in eps * scale: see ACCURACY
 constexpr double kHitMaxScale = 1e300;
 constexpr int32_t kHitFree = -1, kHitOutside = -2, kHitInvalid = -3;
-
-constexpr double hit_binom(int n, int k) {
-  double r = 1.0;
-  for (int j = 0; j < k; ++j) r = r * (double)(n - j) / (double)(j + 1);
-  return r;
-}
 
 // the cell of q on an axis of `size` cells, query's rule; -1 and `size` stand for the two outsides
 __device__ inline int hit_cell(double q, int size) { return q <= -1.0 ? -1 : (q >= (double)size ? size : (int)q); }
@@ -125,13 +121,7 @@ __global__ void __launch_bounds__(64) k_traj_voxel_hit(HitArgs a) {
         sa += fabs(qu[ax][p]);
       }
       bad = bad || !(sa < kHitMaxScale);
-#pragma unroll
-      for (int ii = 0; ii < D; ++ii) {
-        double acc = qu[ax][0];
-#pragma unroll
-        for (int k = 1; k <= ii; ++k) acc = __builtin_fma(hit_binom(ii, k) / hit_binom(n, k), qu[ax][k], acc);
-        bz[ax][ii] = acc;
-      }
+      bern::to_bernstein<D>(qu[ax], bz[ax]);
     }
   }
   if (bad) {
@@ -145,12 +135,7 @@ __global__ void __launch_bounds__(64) k_traj_voxel_hit(HitArgs a) {
     const int64_t id = (int64_t)x + (int64_t)sx * ((int64_t)y + (int64_t)sy * (int64_t)z);
     return vox[id] != 0 ? (int32_t)id : kHitFree;
   };
-  auto horner = [&](const double(&g)[D], double tau) {
-    double v = g[n];
-#pragma unroll
-    for (int k = n - 1; k >= 0; --k) v = __builtin_fma(v, tau, g[k]);
-    return v;
-  };
+  auto horner = [&](const double(&g)[D], double tau) { return bern::horner<D>(g, tau); };
   double tau_hit = INFINITY;
   int32_t vhit = kHitFree;
   bool done = false;

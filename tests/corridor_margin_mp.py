@@ -8,14 +8,16 @@ Everything is built on the exact algebra of tests/trajectory_mp.py: `Fraction` f
 square-free part over QQ, the root count by Sturm sequences, `polyroots` at 60 digits.  The maximum of the exact g over
 {0, 1} and the roots of g' in [0, 1] is the reference; nothing is rounded to double before the caller asks for it.
 
-The `*_mp` functions need mpmath and sympy; `margin_bound`, `row_scales`, `g_float64` need numpy only, so GPU tests can
+The `*_mp` functions need mpmath and sympy; `margin_bound`, `row_scales`, `g_float64`, `margin_float64` need numpy only, so GPU tests can
 import this module without mpmath and read the references from tests/golden/corridor_margin_cases.npz
 (tests/golden/make_corridor_margin_golden.py writes it).
 """
+import math
 from fractions import Fraction as Fr
 
 import numpy as np
 
+from tests import bernstein_np as bnp
 from tests import trajectory_mp as tmp
 from tests.trajectory_mp import _mpf, _pder, _pval, EPS
 
@@ -26,6 +28,8 @@ except ImportError:      # the bound helpers still work
     mpmath = sympy = None
 
 K_MARGIN = 32
+# the kernel's constants (csrc/corridor_margin_kernels.h)
+MARGIN_SLACK, MARGIN_DEPTH, MARGIN_MAX_NODES, MARGIN_BISECT = 8.0, 20, 1024, 48
 
 
 def deriv_exact(cm, T, d):
@@ -132,3 +136,114 @@ def g_float64(cm, T, d, row, t):
     cm = np.asarray(cm, dtype=np.float64)
     v = np.array([np.polyval(np.polyder(cm[ax], d) if d else cm[ax], float(t)) for ax in range(3)])
     return float(np.dot(np.asarray(row[:3], dtype=np.float64), v) - float(row[3]))
+
+
+# ---- the kernel's procedure in plain float64 --------------------------------------------------------------------------------
+def _ff(k, d):
+    r = 1.0
+    for e in range(d):
+        r *= (k - e)
+    return r
+
+
+def margin_float64(cm, T, d, rows, prune=True, stats=None):
+    """k_traj_row_margin statement by statement in plain float64 (no fused operations): (margin, row, t)."""
+    cm = np.asarray(cm, dtype=np.float64)
+    D = cm.shape[1]
+    n = D - 1
+    tk = [1.0]
+    for k in range(1, D):
+        tk.append(tk[-1] * T)
+    asc = np.concatenate([cm[:, ::-1], np.zeros((3, 2))], axis=1)
+    u = np.array([[_ff(k + d, d) * asc[ax, k + d] * tk[k] for k in range(D)] for ax in range(3)])
+    if not (np.isfinite(T) and np.isfinite(cm).all()):
+        return math.nan, -1, 0.0
+    A = np.abs(u).sum(axis=1)
+    p1 = np.zeros(3)
+    bz = np.zeros((3, D))
+    for ax in range(3):
+        s1 = u[ax, n]
+        for k in range(n - 1, -1, -1):
+            s1 = s1 + u[ax, k]
+        p1[ax] = s1
+        bz[ax] = bnp.bernstein(u[ax])
+    best, brow, bt = -math.inf, -1, 0.0
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 4)
+    for r, (ra, rb, rc, rd) in enumerate(rows):                 # first pass: the ends of every row
+        if ra == 0.0 and rb == 0.0 and rc == 0.0 and rd == 0.0:
+            continue
+        if not np.isfinite([ra, rb, rc, rd]).all():
+            return math.nan, -1, 0.0
+        for tau, p in ((0.0, u[:, 0]), (1.0, p1)):
+            g = (rc * p[2] + (rb * p[1] + ra * p[0])) - rd
+            if g > best:
+                best, brow, bt = g, r, tau
+    live = []
+    for r, (ra, rb, rc, rd) in enumerate(rows):                 # second pass: mark the rows that may still raise `best`
+        if ra == 0.0 and rb == 0.0 and rc == 0.0 and rd == 0.0:
+            continue
+        ub = max((rc * bz[2, ii] + (rb * bz[1, ii] + ra * bz[0, ii])) - rd for ii in range(D))
+        scale = abs(rc) * A[2] + (abs(rb) * A[1] + (abs(ra) * A[0] + abs(rd)))
+        if not prune or ub + MARGIN_SLACK * EPS * scale > best:
+            live.append(r)
+        elif stats is not None:
+            stats["pruned"] = stats.get("pruned", 0) + 1
+    for r in live:                                              # third pass: the marked rows, tested again
+        ra, rb, rc, rd = rows[r]
+
+        def dotrow(x, y, z):
+            return (rc * z + (rb * y + ra * x)) - rd
+
+        def candidate(tau):
+            nonlocal best, brow, bt
+            v = []
+            for ax in range(3):
+                h = u[ax, n]
+                for k in range(n - 1, -1, -1):
+                    h = h * tau + u[ax, k]
+                v.append(h)
+            g = dotrow(*v)
+            if g > best:
+                best, brow, bt = g, r, tau
+
+        cv = [dotrow(*bz[:, ii]) for ii in range(D)]
+        scale = abs(rc) * A[2] + (abs(rb) * A[1] + (abs(ra) * A[0] + abs(rd)))
+        if prune and not (max(cv) + MARGIN_SLACK * EPS * scale > best):
+            if stats is not None:
+                stats["pruned"] = stats.get("pruned", 0) + 1
+            continue
+        dv = [cv[k + 1] - cv[k] for k in range(n)]
+        gd = [(k + 1) * (rc * u[2, k + 1] + (rb * u[1, k + 1] + ra * u[0, k + 1])) for k in range(n)]
+        lev, idx = 0, 0
+        for _ in range(MARGIN_MAX_NODES):
+            var, first, mx = bnp.sign_scan(bnp.descend(dv, lev, idx))
+            width = math.ldexp(1.0, -lev)
+            lo = idx * width
+            mid = lo + 0.5 * width
+            split = False
+            if var == 0:
+                pass
+            elif n * mx * width <= EPS * scale:
+                candidate(mid)
+            elif var == 1:
+                if first > 0:
+                    lo_, hi_ = lo, lo + width
+                    for _it in range(MARGIN_BISECT):
+                        mm = 0.5 * (lo_ + hi_)
+                        fm = gd[n - 1]
+                        for k in range(n - 2, -1, -1):
+                            fm = fm * mm + gd[k]
+                        if fm > 0.0:
+                            lo_ = mm
+                        else:
+                            hi_ = mm
+                    candidate(0.5 * (lo_ + hi_))
+            else:
+                candidate(mid)
+                split = lev < MARGIN_DEPTH
+            if stats is not None:
+                stats["nodes"] = stats.get("nodes", 0) + 1
+            lev, idx, more = bnp.advance(lev, idx, split)
+            if not more:
+                break
+    return best, brow, bt * T

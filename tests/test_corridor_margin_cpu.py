@@ -19,148 +19,13 @@ from tests.util import GOLDEN
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_NAMES = ["anet_traj_row_margin", "anet_traj_row_margin_dev"]
 EPS = cmm.EPS
-# the kernel's constants (csrc/corridor_margin_kernels.h)
-SLACK, MAX_DEPTH, MAX_NODES, BISECT = 8.0, 20, 1024, 48
+SLACK, MAX_DEPTH, MAX_NODES, BISECT = cmm.MARGIN_SLACK, cmm.MARGIN_DEPTH, cmm.MARGIN_MAX_NODES, cmm.MARGIN_BISECT
+margin_float64 = cmm.margin_float64
 
 
 @pytest.fixture(scope="module")
 def fx():
     return np.load(os.path.join(GOLDEN, "corridor_margin_cases.npz"))
-
-
-def _ff(k, d):
-    r = 1.0
-    for e in range(d):
-        r *= (k - e)
-    return r
-
-
-def margin_float64(cm, T, d, rows, prune=True, stats=None):
-    """k_traj_row_margin statement by statement in plain float64 (no fused operations): (margin, row, t)."""
-    cm = np.asarray(cm, dtype=np.float64)
-    D = cm.shape[1]
-    n = D - 1
-    tk = [1.0]
-    for k in range(1, D):
-        tk.append(tk[-1] * T)
-    asc = np.concatenate([cm[:, ::-1], np.zeros((3, 2))], axis=1)
-    u = np.array([[_ff(k + d, d) * asc[ax, k + d] * tk[k] for k in range(D)] for ax in range(3)])
-    if not (np.isfinite(T) and np.isfinite(cm).all()):
-        return math.nan, -1, 0.0
-    A = np.abs(u).sum(axis=1)
-    p1 = np.zeros(3)
-    bz = np.zeros((3, D))
-    for ax in range(3):
-        s1 = u[ax, n]
-        for k in range(n - 1, -1, -1):
-            s1 = s1 + u[ax, k]
-        p1[ax] = s1
-        for ii in range(D):
-            acc = u[ax, 0]
-            for k in range(1, ii + 1):
-                acc = acc + (math.comb(ii, k) / math.comb(n, k)) * u[ax, k]
-            bz[ax, ii] = acc
-    best, brow, bt = -math.inf, -1, 0.0
-    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 4)
-    for r, (ra, rb, rc, rd) in enumerate(rows):                 # first pass: the ends of every row
-        if ra == 0.0 and rb == 0.0 and rc == 0.0 and rd == 0.0:
-            continue
-        if not np.isfinite([ra, rb, rc, rd]).all():
-            return math.nan, -1, 0.0
-        for tau, p in ((0.0, u[:, 0]), (1.0, p1)):
-            g = (rc * p[2] + (rb * p[1] + ra * p[0])) - rd
-            if g > best:
-                best, brow, bt = g, r, tau
-    live = []
-    for r, (ra, rb, rc, rd) in enumerate(rows):                 # second pass: mark the rows that may still raise `best`
-        if ra == 0.0 and rb == 0.0 and rc == 0.0 and rd == 0.0:
-            continue
-        ub = max((rc * bz[2, ii] + (rb * bz[1, ii] + ra * bz[0, ii])) - rd for ii in range(D))
-        scale = abs(rc) * A[2] + (abs(rb) * A[1] + (abs(ra) * A[0] + abs(rd)))
-        if not prune or ub + SLACK * EPS * scale > best:
-            live.append(r)
-        elif stats is not None:
-            stats["pruned"] = stats.get("pruned", 0) + 1
-    for r in live:                                              # third pass: the marked rows, tested again
-        ra, rb, rc, rd = rows[r]
-
-        def dotrow(x, y, z):
-            return (rc * z + (rb * y + ra * x)) - rd
-
-        def candidate(tau):
-            nonlocal best, brow, bt
-            v = []
-            for ax in range(3):
-                h = u[ax, n]
-                for k in range(n - 1, -1, -1):
-                    h = h * tau + u[ax, k]
-                v.append(h)
-            g = dotrow(*v)
-            if g > best:
-                best, brow, bt = g, r, tau
-
-        cv = [dotrow(*bz[:, ii]) for ii in range(D)]
-        scale = abs(rc) * A[2] + (abs(rb) * A[1] + (abs(ra) * A[0] + abs(rd)))
-        if prune and not (max(cv) + SLACK * EPS * scale > best):
-            if stats is not None:
-                stats["pruned"] = stats.get("pruned", 0) + 1
-            continue
-        dv = [cv[k + 1] - cv[k] for k in range(n)]
-        gd = [(k + 1) * (rc * u[2, k + 1] + (rb * u[1, k + 1] + ra * u[0, k + 1])) for k in range(n)]
-        lev, idx = 0, 0
-        for _ in range(MAX_NODES):
-            w = list(dv)
-            for lv in range(lev):
-                right = (idx >> (lev - 1 - lv)) & 1
-                le, ri = [0.0] * n, [0.0] * n
-                le[0], ri[n - 1] = w[0], w[n - 1]
-                for q in range(1, n):
-                    for k in range(n - q):
-                        w[k] = 0.5 * (w[k] + w[k + 1])
-                    le[q] = w[0]
-                    ri[n - 1 - q] = w[n - 1 - q]
-                w = ri if right else le
-            sg = [int(x > 0.0) - int(x < 0.0) for x in w]
-            nz = [x for x in sg if x != 0]
-            var = sum(1 for p, q in zip(nz, nz[1:]) if p != q)
-            first = nz[0] if nz else 0
-            mx = max(abs(x) for x in w)
-            width = math.ldexp(1.0, -lev)
-            lo = idx * width
-            mid = lo + 0.5 * width
-            split = False
-            if var == 0:
-                pass
-            elif n * mx * width <= EPS * scale:
-                candidate(mid)
-            elif var == 1:
-                if first > 0:
-                    lo_, hi_ = lo, lo + width
-                    for _it in range(BISECT):
-                        mm = 0.5 * (lo_ + hi_)
-                        fm = gd[n - 1]
-                        for k in range(n - 2, -1, -1):
-                            fm = fm * mm + gd[k]
-                        if fm > 0.0:
-                            lo_ = mm
-                        else:
-                            hi_ = mm
-                    candidate(0.5 * (lo_ + hi_))
-            else:
-                candidate(mid)
-                split = lev < MAX_DEPTH
-            if stats is not None:
-                stats["nodes"] = stats.get("nodes", 0) + 1
-            if split:
-                lev, idx = lev + 1, idx << 1
-            else:
-                while lev > 0 and (idx & 1):
-                    idx >>= 1
-                    lev -= 1
-                if lev == 0:
-                    break
-                idx += 1
-    return best, brow, bt * T
 
 
 # ---- the reference against facts that do not depend on it ---------------------------------------------------

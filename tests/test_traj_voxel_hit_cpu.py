@@ -32,123 +32,7 @@ def grids_of(fx):
             (hm.Grid((1, 1, 1), (0.0, 0.0, 0.0), 1.0), np.zeros(1, dtype=np.uint8))]
 
 
-def hit_float64(cm, T, grid, vox, max_nodes=hm.HIT_MAX_NODES, stats=None):
-    """k_traj_voxel_hit statement by statement in plain float64 (no fused operations): (t_hit, voxel)."""
-    cm = np.asarray(cm, dtype=np.float64)
-    D = cm.shape[1]
-    n = D - 1
-    size = grid.size
-    if not (T >= 0.0 and T < math.inf and np.isfinite(cm).all()):
-        return math.nan, hm.HIT_INVALID
-    tk = [1.0]
-    for k in range(1, D):
-        tk.append(tk[-1] * T)
-    qu = np.array([[((cm[ax, n] - grid.origin[ax]) if p == 0 else cm[ax, n - p] * tk[p]) / grid.scale for p in range(D)]
-                   for ax in range(3)])
-    if not (np.abs(qu).sum(axis=1) < 1e300).all():
-        return math.nan, hm.HIT_INVALID
-    bz = np.zeros((3, D))
-    for ax in range(3):
-        for ii in range(D):
-            acc = qu[ax, 0]
-            for k in range(1, ii + 1):
-                acc = acc + (math.comb(ii, k) / math.comb(n, k)) * qu[ax, k]
-            bz[ax, ii] = acc
-
-    def horner(g, tau):
-        v = g[n]
-        for k in range(n - 1, -1, -1):
-            v = v * tau + g[k]
-        return v
-
-    probe = lambda c: hm.probe(c, grid, vox)
-    lev, idx = 0, 0
-    for _ in range(max_nodes):
-        width = math.ldexp(1.0, -lev)
-        aa, bb = idx * width, (idx + 1) * width
-        rr = aa / bb
-        mn, mx, w0, wn, mono = [], [], [], [], []
-        for ax in range(3):
-            w = list(bz[ax])
-            if bb < 1.0:
-                le = [w[0]]
-                for q in range(1, D):
-                    for k in range(D - q):
-                        w[k] = w[k] + bb * (w[k + 1] - w[k])
-                    le.append(w[0])
-                w = le
-            if aa > 0.0:
-                ri = [0.0] * D
-                ri[n] = w[n]
-                for q in range(1, D):
-                    for k in range(D - q):
-                        w[k] = w[k] + rr * (w[k + 1] - w[k])
-                    ri[n - q] = w[n - q]
-                w = ri
-            mn.append(min(w)); mx.append(max(w)); w0.append(w[0]); wn.append(w[n])
-            up = all(w[k] > w[k - 1] for k in range(1, D))
-            down = all(w[k] < w[k - 1] for k in range(1, D))
-            mono.append(1 if up else -1 if down else 0)
-        lo = [hm.cell_of(mn[ax], size[ax]) for ax in range(3)]
-        hi = [hm.cell_of(mx[ax], size[ax]) for ax in range(3)]
-        cnt = [hi[ax] - lo[ax] + 1 for ax in range(3)]
-        count = cnt[0] * cnt[1] * cnt[2]
-        split = decided = False
-        hit = None
-        if stats is not None:
-            stats["nodes"] = stats.get("nodes", 0) + 1
-        if count <= hm.HIT_BOX_CELLS:
-            cells = [(x, y, z) for z in range(lo[2], hi[2] + 1) for y in range(lo[1], hi[1] + 1) for x in range(lo[0], hi[0] + 1)]
-            if stats is not None:
-                stats["lookups"] = stats.get("lookups", 0) + len(cells)
-            if not any(probe(c) != hm.HIT_FREE for c in cells):
-                decided = True
-            else:
-                c0 = [hm.cell_of(w0[ax], size[ax]) for ax in range(3)]
-                at = probe(tuple(c0))
-                if at != hm.HIT_FREE:
-                    hit, decided = (aa, at), True
-                elif count == 2:
-                    ax = cnt.index(2)
-                    if mono[ax] != 0:
-                        decided = True
-                        if hm.cell_of(wn[ax], size[ax]) != c0[ax]:
-                            lo_, hi_ = aa, bb
-                            for _it in range(hm.HIT_BISECT):
-                                m = 0.5 * (lo_ + hi_)
-                                if not (lo_ < m < hi_):
-                                    break
-                                if hm.cell_of(horner(qu[ax], m), size[ax]) != c0[ax]:
-                                    hi_ = m
-                                else:
-                                    lo_ = m
-                            other = list(c0)
-                            other[ax] = c0[ax] + 1 if c0[ax] == lo[ax] else c0[ax] - 1
-                            hit = (hi_, probe(tuple(other)))
-                            if stats is not None:
-                                stats["bisect"] = stats.get("bisect", 0) + 1
-        if not decided:
-            if lev < hm.HIT_DEPTH:
-                split = True
-            else:
-                m = 0.5 * (aa + bb)
-                at = probe(tuple(hm.cell_of(horner(qu[ax], m), size[ax]) for ax in range(3)))
-                if at != hm.HIT_FREE:
-                    hit = (aa, at)
-                if stats is not None:
-                    stats["depth"] = stats.get("depth", 0) + 1
-        if hit is not None:
-            return hit[0] * T, hit[1]
-        if split:
-            lev, idx = lev + 1, idx << 1
-        else:
-            while lev > 0 and (idx & 1):
-                idx >>= 1
-                lev -= 1
-            if lev == 0:
-                return math.inf, hm.HIT_FREE
-            idx += 1
-    return idx * math.ldexp(1.0, -lev) * T, hm.HIT_INVALID
+hit_float64 = hm.hit_float64
 
 
 # ---- the reference against facts that do not depend on it ---------------------------------------------------

@@ -13,10 +13,10 @@ The `*_mp` functions need mpmath and sympy; `clearance_bound`, `scales`, `cleara
 the references from tests/golden/traj_clearance_cases.npz (tests/golden/make_traj_clearance_golden.py writes it).
 """
 from fractions import Fraction as Fr
-from math import comb
 
 import numpy as np
 
+from tests import bernstein_np as bnp
 from tests import corridor_margin_mp as cmm
 from tests import trajectory_mp as tmp
 from tests.trajectory_mp import _mpf, _pder, _pmul, _padd, _pval, EPS
@@ -212,11 +212,6 @@ def cap_of(family, s):
 
 
 # ---- the kernel's procedure in plain float64 --------------------------------------------------------------------------------
-def bernstein(ua):
-    n = len(ua) - 1
-    return np.array([sum(comb(i, k) / comb(n, k) * ua[k] for k in range(i + 1)) for i in range(n + 1)])
-
-
 def _horner(ua, tau):
     v = ua[-1]
     for c in ua[-2::-1]:
@@ -256,7 +251,7 @@ def clearance_float64(cm, T, pts, count=None, stats=None):
         return np.nan, -1, 0.0
     cnt = len(pts) if count is None else min(max(int(count), 0), len(pts))
     A1 = float(np.abs(u).sum())
-    bz = np.stack([bernstein(u[ax]) for ax in range(3)])
+    bz = np.stack([bnp.bernstein(u[ax]) for ax in range(3)])
     taus = np.arange(CLR_K) / (CLR_K - 1)
     pos = np.stack([[_horner(u[ax], t) for t in taus] for ax in range(3)])           # (3, K)
     Lh2 = float(np.sqrt((np.diff(bz, axis=1) ** 2).sum(axis=0).max())) * (n * 0.5 / (CLR_K - 1))
@@ -272,7 +267,6 @@ def clearance_float64(cm, T, pts, count=None, stats=None):
         d2, k = nearest(pts[j])
         if d2 < best2:
             best2, bp, bt = d2, j, taus[k]
-    wts = np.array([[comb(n, i) * comb(n - 1, j) / comb(2 * n - 1, i + j) for j in range(n)] for i in range(n + 1)])
 
     def thr2(q):
         sc = A1 + float(np.abs(q).sum())
@@ -293,28 +287,10 @@ def clearance_float64(cm, T, pts, count=None, stats=None):
             if d2 < best2:
                 best2, bp, bt = float(d2), j, float(tau)
 
-        dots = np.einsum("ai,aj->ij", bz - q[:, None], np.diff(bz, axis=1))
-        dv = np.zeros(M)
-        for i in range(n + 1):
-            for jj in range(n):
-                dv[i + jj] += wts[i, jj] * dots[i, jj]
+        dv = bnp.product_cv(bz - q[:, None], bz)
         lev, idx, done = 0, 0, False
         for _ in range(CLR_MAX_NODES):
-            w = dv.copy()
-            for l in range(lev):
-                right = (idx >> (lev - 1 - l)) & 1
-                le = np.empty(M)
-                le[0] = w[0]
-                for r in range(1, M):
-                    w[:M - r] = 0.5 * (w[:M - r] + w[1:M - r + 1])
-                    le[r] = w[0]
-                if not right:
-                    w = le
-            sg = np.sign(w)
-            nz = sg[sg != 0]
-            var = int((nz[1:] != nz[:-1]).sum()) if len(nz) else 0
-            first = int(nz[0]) if len(nz) else 0
-            mx = float(np.abs(w).max())
+            var, first, mx = bnp.sign_scan(bnp.descend(dv, lev, idx))
             width = 2.0 ** -lev
             lo = idx * width
             mid = lo + 0.5 * width
@@ -341,17 +317,10 @@ def clearance_float64(cm, T, pts, count=None, stats=None):
                 split = lev < CLR_DEPTH
                 if not split:
                     st["depth_out"] += 1
-            if split:
-                lev += 1
-                idx <<= 1
-            else:
-                while lev > 0 and (idx & 1):
-                    idx >>= 1
-                    lev -= 1
-                if lev == 0:
-                    done = True
-                    break
-                idx += 1
+            lev, idx, more = bnp.advance(lev, idx, split)
+            if not more:
+                done = True
+                break
         if not done:
             st["nodes_out"] += 1
     if bp < 0:

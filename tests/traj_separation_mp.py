@@ -14,10 +14,10 @@ so GPU tests read the references from tests/golden/traj_separation_cases.npz (te
 """
 import math
 from fractions import Fraction as Fr
-from math import comb
 
 import numpy as np
 
+from tests import bernstein_np as bnp
 from tests import corridor_margin_mp as cmm
 from tests import trajectory_mp as tmp
 from tests.trajectory_mp import _mpf, _pder, _pmul, _padd, _pval, EPS
@@ -266,7 +266,7 @@ def _load(cm, T):
         tk = np.cumprod(np.r_[1.0, np.full(n, float(T))])
         u = cm[:, ::-1] * tk[None]
     ok = bool(np.all(np.isfinite(cm)) and np.all(np.isfinite(u)))
-    z = np.array([[sum(comb(i, k) / comb(n, k) * u[ax, k] for k in range(i + 1)) for i in range(n + 1)] for ax in range(3)]) if ok else None
+    z = np.stack([bnp.bernstein(u[ax]) for ax in range(3)]) if ok else None
     return ok, z, float(np.abs(u).sum()) if ok else 0.0
 
 
@@ -316,7 +316,6 @@ def separation_float64(co, T, t0, a, b, cutoff=np.inf, stats=None):
         KNa, KNb = knots(T[a], K0a)[-1], knots(T[b], K0b)[-1]
     if not (np.all(np.isfinite(T[[a, b]])) and np.all(T[[a, b]] >= 0.0) and np.all(np.isfinite([K0a, K0b, KNa, KNb]))):
         return np.nan, 0.0, -1, -1
-    wts = np.array([[comb(n, i) * comb(n - 1, j) / comb(2 * n - 1, i + j) for j in range(n)] for i in range(n + 1)])
     ia = ib = 0
     la = lb = -1
     Tia, Tib = float(T[a, 0]), float(T[b, 0])
@@ -376,28 +375,10 @@ def separation_float64(co, T, t0, a, b, cutoff=np.inf, stats=None):
         if ub2 < thr * thr * (1.0 + 8.0 * EPS):
             st["survivors"] += 1
             flat = (EPS * sc) ** 2
-            dots = np.einsum("ai,aj->ij", d, np.diff(d, axis=1))
-            dv = np.zeros(M)
-            for i in range(n + 1):
-                for jj in range(n):
-                    dv[i + jj] += wts[i, jj] * dots[i, jj]
+            dv = bnp.product_cv(d, d)
             lev, idx, done = 0, 0, False
             for _ in range(SEP_MAX_NODES):
-                w = dv.copy()
-                for l in range(lev):
-                    right = (idx >> (lev - 1 - l)) & 1
-                    le = np.empty(M)
-                    le[0] = w[0]
-                    for r in range(1, M):
-                        w[:M - r] = 0.5 * (w[:M - r] + w[1:M - r + 1])
-                        le[r] = w[0]
-                    if not right:
-                        w = le
-                sg_ = np.sign(w)
-                nz = sg_[sg_ != 0]
-                var = int((nz[1:] != nz[:-1]).sum()) if len(nz) else 0
-                first = int(nz[0]) if len(nz) else 0
-                mx = float(np.abs(w).max())
+                var, first, mx = bnp.sign_scan(bnp.descend(dv, lev, idx))
                 width = 2.0 ** -lev
                 l0 = idx * width
                 mid = l0 + 0.5 * width
@@ -426,17 +407,10 @@ def separation_float64(co, T, t0, a, b, cutoff=np.inf, stats=None):
                     split = lev < SEP_DEPTH
                     if not split:
                         st["depth_out"] += 1
-                if split:
-                    lev += 1
-                    idx <<= 1
-                else:
-                    while lev > 0 and (idx & 1):
-                        idx >>= 1
-                        lev -= 1
-                    if lev == 0:
-                        done = True
-                        break
-                    idx += 1
+                lev, idx, more = bnp.advance(lev, idx, split)
+                if not more:
+                    done = True
+                    break
             if not done:
                 st["nodes_out"] += 1
         lo = hi

@@ -9,14 +9,16 @@ doubles, square-free part over QQ, root count by Sturm sequences, `polyroots` at
 plane q = 1 .. size - 1 and of the two map-boundary planes q = -1, q = size is a polynomial root; the roots are sorted, the
 midpoint of each gap gives the cell occupied there, and the first blocked gap gives t*, the voxel and the crossing axis.
 
-The `*_mp` functions need mpmath and sympy; `hit_bound`, `tol_pos`, `cells_float64` need numpy only, so GPU tests read the
+The `*_mp` functions need mpmath and sympy; `hit_bound`, `tol_pos`, `cells_float64`, `hit_float64` need numpy only, so GPU tests read the
 references from tests/golden/traj_voxel_hit_cases.npz (tests/golden/make_traj_voxel_hit_golden.py writes it).
 """
+import math
 from fractions import Fraction as Fr
 
 import numpy as np
 
 from tests import corridor_margin_mp as cmm
+from tests.bernstein_np import advance, bernstein
 from tests import trajectory_mp as tmp
 from tests.trajectory_mp import _mpf, _pder, _pval, EPS
 
@@ -156,13 +158,6 @@ def hit_bound(T, scale, dq):
     return T * 2.0 ** -HIT_DEPTH + HIT_C * EPS * scale / dq * T
 
 
-def bernstein(qa):
-    """control values on [0, 1] of ascending coefficients (float64)"""
-    from math import comb
-    n = len(qa) - 1
-    return np.array([sum(comb(i, k) / comb(n, k) * qa[k] for k in range(i + 1)) for i in range(n + 1)])
-
-
 def tol_pos(cm, T, grid):
     """The band, in voxels, inside which either answer is allowed: max(2^-HIT_DEPTH L, HIT_C EPS scale_i); L the arc-length bound
     n max_k |b_k+1 - b_k| from the derivative control values, scale_i = max over the axes of sum_k |u_ax,k| + the largest |plane| the
@@ -213,3 +208,111 @@ def cells_float64(cm, T, grid, t):
     p = np.array([np.polyval(cm[ax], float(t)) for ax in range(3)])
     qv = (p - np.array(grid.origin)) / grid.scale
     return tuple(cell_of(float(qv[ax]), grid.size[ax]) for ax in range(3))
+
+
+# ---- the kernel's procedure in plain float64 --------------------------------------------------------------------------------
+def hit_float64(cm, T, grid, vox, max_nodes=HIT_MAX_NODES, stats=None):
+    """k_traj_voxel_hit statement by statement in plain float64 (no fused operations): (t_hit, voxel)."""
+    cm = np.asarray(cm, dtype=np.float64)
+    D = cm.shape[1]
+    n = D - 1
+    size = grid.size
+    if not (T >= 0.0 and T < math.inf and np.isfinite(cm).all()):
+        return math.nan, HIT_INVALID
+    tk = [1.0]
+    for k in range(1, D):
+        tk.append(tk[-1] * T)
+    qu = np.array([[((cm[ax, n] - grid.origin[ax]) if p == 0 else cm[ax, n - p] * tk[p]) / grid.scale for p in range(D)]
+                   for ax in range(3)])
+    if not (np.abs(qu).sum(axis=1) < 1e300).all():
+        return math.nan, HIT_INVALID
+    bz = np.stack([bernstein(qu[ax]) for ax in range(3)])
+
+    def horner(g, tau):
+        v = g[n]
+        for k in range(n - 1, -1, -1):
+            v = v * tau + g[k]
+        return v
+
+    look = lambda c: probe(c, grid, vox)
+    lev, idx = 0, 0
+    for _ in range(max_nodes):
+        width = math.ldexp(1.0, -lev)
+        aa, bb = idx * width, (idx + 1) * width
+        rr = aa / bb
+        mn, mx, w0, wn, mono = [], [], [], [], []
+        for ax in range(3):
+            w = list(bz[ax])
+            if bb < 1.0:
+                le = [w[0]]
+                for q in range(1, D):
+                    for k in range(D - q):
+                        w[k] = w[k] + bb * (w[k + 1] - w[k])
+                    le.append(w[0])
+                w = le
+            if aa > 0.0:
+                ri = [0.0] * D
+                ri[n] = w[n]
+                for q in range(1, D):
+                    for k in range(D - q):
+                        w[k] = w[k] + rr * (w[k + 1] - w[k])
+                    ri[n - q] = w[n - q]
+                w = ri
+            mn.append(min(w)); mx.append(max(w)); w0.append(w[0]); wn.append(w[n])
+            up = all(w[k] > w[k - 1] for k in range(1, D))
+            down = all(w[k] < w[k - 1] for k in range(1, D))
+            mono.append(1 if up else -1 if down else 0)
+        lo = [cell_of(mn[ax], size[ax]) for ax in range(3)]
+        hi = [cell_of(mx[ax], size[ax]) for ax in range(3)]
+        cnt = [hi[ax] - lo[ax] + 1 for ax in range(3)]
+        count = cnt[0] * cnt[1] * cnt[2]
+        split = decided = False
+        hit = None
+        if stats is not None:
+            stats["nodes"] = stats.get("nodes", 0) + 1
+        if count <= HIT_BOX_CELLS:
+            cells = [(x, y, z) for z in range(lo[2], hi[2] + 1) for y in range(lo[1], hi[1] + 1) for x in range(lo[0], hi[0] + 1)]
+            if stats is not None:
+                stats["lookups"] = stats.get("lookups", 0) + len(cells)
+            if not any(look(c) != HIT_FREE for c in cells):
+                decided = True
+            else:
+                c0 = [cell_of(w0[ax], size[ax]) for ax in range(3)]
+                at = look(tuple(c0))
+                if at != HIT_FREE:
+                    hit, decided = (aa, at), True
+                elif count == 2:
+                    ax = cnt.index(2)
+                    if mono[ax] != 0:
+                        decided = True
+                        if cell_of(wn[ax], size[ax]) != c0[ax]:
+                            lo_, hi_ = aa, bb
+                            for _it in range(HIT_BISECT):
+                                m = 0.5 * (lo_ + hi_)
+                                if not (lo_ < m < hi_):
+                                    break
+                                if cell_of(horner(qu[ax], m), size[ax]) != c0[ax]:
+                                    hi_ = m
+                                else:
+                                    lo_ = m
+                            other = list(c0)
+                            other[ax] = c0[ax] + 1 if c0[ax] == lo[ax] else c0[ax] - 1
+                            hit = (hi_, look(tuple(other)))
+                            if stats is not None:
+                                stats["bisect"] = stats.get("bisect", 0) + 1
+        if not decided:
+            if lev < HIT_DEPTH:
+                split = True
+            else:
+                m = 0.5 * (aa + bb)
+                at = look(tuple(cell_of(horner(qu[ax], m), size[ax]) for ax in range(3)))
+                if at != HIT_FREE:
+                    hit = (aa, at)
+                if stats is not None:
+                    stats["depth"] = stats.get("depth", 0) + 1
+        if hit is not None:
+            return hit[0] * T, hit[1]
+        lev, idx, more = advance(lev, idx, split)
+        if not more:
+            return math.inf, HIT_FREE
+    return idx * math.ldexp(1.0, -lev) * T, HIT_INVALID
