@@ -38,6 +38,9 @@ from . import flatness  # noqa: F401
 from .flatness import (FlatnessMap, flat_forward, flat_forward_dev, flat_backward, flat_backward_dev,  # noqa: F401
                        traj_flat_states, traj_flat_extrema, make_flat_params, make_flat_penalty, minco_flat_cost_grad,
                        minco_flat_cost_grad_dev, minco_flat_partial_grads_dev)
+from . import avoid  # noqa: F401
+from .avoid import (AvoidOthers, make_avoid_penalty, minco_avoid_partial_grads_dev, minco_avoid_cost_grad_dev,  # noqa: F401
+                    minco_avoid_cost_grad, neighbours_all, neighbours_from_pairs, upload_others, avoid_objective_dev)
 from . import time_net  # noqa: F401
 from .time_net import TimeAllocNet  # noqa: F401
 from . import learning_planner  # noqa: F401

@@ -131,6 +131,8 @@ PROTOTYPES = {
                                  c_void_p, c_double] + [c_void_p] * 5),
     "anet_traj_separation": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                              c_double] + [c_void_p] * 4),
+    "anet_minco_avoid_partial_grads_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                                   c_int, c_int64, c_int64] + [c_void_p] * 5 + [c_int] + [c_void_p] * 5),
     "anet_voxel_path_workspace": (c_int64, [c_void_p, c_int64]),
     "anet_voxel_path_field_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                           c_void_p]),
@@ -242,6 +244,11 @@ class FlatPenalty(ctypes.Structure):
     _fields_ = [("w_thrust", c_double), ("w_tilt", c_double), ("w_bdr", c_double), ("smooth_mu", c_double),
                 ("min_thrust", c_double), ("max_thrust", c_double), ("max_tilt", c_double), ("max_bdr", c_double),
                 ("res", ctypes.c_int32)]
+
+
+class AvoidPenalty(ctypes.Structure):
+    """struct anet_avoid_penalty (include/allocnet_amd.h)."""
+    _fields_ = [("w", c_double), ("smooth_mu", c_double), ("min_dist", c_double), ("z_scale", c_double), ("res", ctypes.c_int32)]
 
 
 _lib = None

@@ -403,13 +403,6 @@ struct FlatPieceGradArgs {
   FlatPenalty pp;
 };
 
-// old + v in two roundings, never one fused operation: with `accumulate` the result is bit for bit the sum of the two separate
-// results
-__device__ __forceinline__ double add_unfused(double old, double v) {
-#pragma clang fp contract(off)
-  return old + v;
-}
-
 // One lane per (trajectory, piece), blockIdx.y = piece, as k_piece_grad.
 //   J_flat = sum_i (T_i/res) sum_{j<res} [ w_thr (phi(thr - thr_max) + phi(thr_min - thr)) + w_tilt phi(cos(tilt_max) - cos(tilt))
 //                                        + w_bdr phi(|omg|^2 - bdr_max^2) ]   at t_j = j T_i / res, psi = dpsi = 0,

@@ -150,4 +150,11 @@ __device__ __forceinline__ double duration_grad(const double csum, const double 
   return csum * inv_res + rT * (acc - __builtin_fma(2.0, Rs2, Rs1));
 }
 
+// old + v in two roundings, never one fused operation: with `accumulate` the result of k_flat_piece_grad and k_minco_avoid is bit for
+// bit the sum of the two separate results
+__device__ __forceinline__ double add_unfused(double old, double v) {
+#pragma clang fp contract(off)
+  return old + v;
+}
+
 }  // namespace anet

@@ -917,6 +917,55 @@ int anet_traj_separation(anet_ctx *ctx, int s, int n_pieces, int64_t batch, cons
                          const double *t0 /* [batch] or NULL */, int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b,
                          double cutoff, double *sep, double *t, int32_t *piece_a, int32_t *piece_b);
 
+/* ---- trajectory avoidance as a penalty of the MINCO objective (no counterpart in the reference) -----------------------------
+ * What anet_traj_separation finds, this term removes: B EGO trajectories are kept min_dist away from listed neighbours of an OTHER
+ * set of Bo piecewise polynomials of the same order s -- other vehicles at a frozen iterate, moving obstacles.  The others are
+ * constants of the objective; their buffers may be the ego buffers themselves (everything is read only).
+ *   ego     coeffs [n_pieces*3*2s][ld], T [n_pieces][ld]: the layout of anet_minco_partial_grads_dev (column col holds the power
+ *           k = 2s - 1 - col); t0 [batch] or NULL (= 0).
+ *   others  o_coeffs [o_pieces*3*2s][o_ld], o_T [o_pieces][o_ld], o_t0 [o_batch] or NULL.  A piece with o_T = 0 is padding and is
+ *           never located: others of different lengths share one buffer.
+ *   lists   CSR: nbr_start int32 [batch + 1], nbr int32 [nbr_start[batch]], indices into the other set.  Ego b is penalised against
+ *           nbr[nbr_start[b] .. nbr_start[b+1]), in that order; the kernel never adds or removes a neighbour (leaving b out of its
+ *           own list when the sets alias is the caller's job).
+ * Knots are float64 by definition, as for anet_traj_separation: K_0 = t0, K_(i+1) = K_i + T_i summed in piece order; the knots L_m
+ * of an other likewise.  Sample j < res of ego piece i:
+ *     sigma = (double)j / (double)res,  tau = sigma * T_i,  t = K_i + tau      one rounding each, nothing contracted into an FMA
+ * The located piece of other o is the m with L_m <= t < L_(m+1) and L_(m+1) > L_m, evaluated at u = t - L_m.  t < L_0 or
+ * t >= L_No: the other is not there and contributes exactly nothing (holding position is not a mode: prepend or append a constant
+ * piece).
+ *     r = p_b,i(tau) - p_o,m(u),   q = r_x^2 + r_y^2 + (r_z / z_scale)^2,   Phi = w smoothedL1_mu(min_dist^2 - q)
+ *     J_avoid(b) = sum_i (T_i / res) sum_(j < res) sum_(o in nbr(b)) Phi        the left Riemann sum of J_pen and J_flat
+ * Partial gradients with coefficients and durations independent, as anet_minco_partial_grads_dev; rt = (r_x, r_y, r_z / z_scale^2),
+ * F = sum_o -2 w phi' rt,  G = sum_o (-2 w phi' rt) . v_o,m(u):
+ *     dJ/dc[i][ax][k] = (T_i/res) sum_j F_ax tau^k
+ *     dJ/dT_i         = (1/res) sum_j sum Phi + (T_i/res) sum_j sigma (F . v_b,i(tau) - G) + sum_(i' > i) S_i'
+ *     S_i             = -(T_i/res) sum_j G      (a later knot moves every later sample in global time),    dJ/dt0_b = sum_i S_i
+ * The indicator "o is there" and the piece switch of an other are differentiated almost everywhere: neither has a gradient.
+ * gdC, gdT, piece_cost (may be NULL): the shapes of anet_minco_partial_grads_dev; gd_t0 [ld] (may be NULL).  accumulate = 0: they
+ * are written; != 0: the kernel's complete share is added to the stored value with one unfused addition, bit for bit the sum of
+ * the two separate results (anet_minco_flat_partial_grads_dev), gd_t0 included.  Lanes in [batch, ld) are never touched.
+ * NaN in every output of ego b, and of b only: a duration, t0 or knot of b that is not finite, a duration of b <= 0; a neighbour
+ * index outside [0, o_batch) (nothing is read for it); a duration or knot of a listed neighbour that is not finite, a negative
+ * duration of one.  An ego with an empty list, or whose every term is inactive, gets exact zeros.
+ * Deterministic: no atomics; the outputs of ego b have the same bits whether b is alone in the launch or one of many and whatever
+ * ld and o_ld are; they may depend on the order of b's list.  No workspace.  Orders 2, 3, 4 (ANET_ERR_UNSUPPORTED otherwise);
+ * ANET_ERR_INVALID: a NULL pointer other than t0, o_t0, piece_cost, gd_t0; ld < batch, o_ld < o_batch; piece counts outside
+ * [1, ANET_MAX_PIECES]; a penalty outside the ranges below.  batch == 0 returns ANET_OK and touches nothing.                  */
+typedef struct anet_avoid_penalty {
+  double w;         /* weight, >= 0 */
+  double smooth_mu; /* smoothedL1 mu in m^2, > 0 */
+  double min_dist;  /* metres, > 0 */
+  double z_scale;   /* > 0; 1 = sphere, > 1 = taller keep-out (downwash) */
+  int32_t res;      /* samples per ego piece, >= 1 */
+} anet_avoid_penalty;
+int anet_minco_avoid_partial_grads_dev(anet_ctx *ctx, const anet_avoid_penalty *pen, int s, int n_pieces, int64_t batch, int64_t ld,
+                                       const double *coeffs, const double *T, const double *t0 /* [batch] or NULL */, int o_pieces,
+                                       int64_t o_batch, int64_t o_ld, const double *o_coeffs, const double *o_T,
+                                       const double *o_t0 /* [o_batch] or NULL */, const int32_t *nbr_start, const int32_t *nbr,
+                                       int accumulate, double *gdC, double *gdT, double *piece_cost /* may be NULL */,
+                                       double *gd_t0 /* [ld], may be NULL */, void *stream);
+
 /* ---- front-end route on the voxel map: sfc_gen::planPath ----------------------------------------------------------------
  * A collision-free polyline from s to g and its length, by a shortest-path field on the grid, a walk back along it and a
  * line-of-sight shortcut; exact and deterministic (no time budget).  box = {lb[3], hb[3]} (host array), the planner's
