@@ -31,7 +31,7 @@ from .sfc_opt import (sfc_overlap_vertices, sfc_overlap_vertices_dev, sfc_forwar
                       sfc_default_max_verts, SFC_NO_OVERLAP)
 
 from . import voxel_map  # noqa: F401
-from .voxel_map import VoxelMap, gather_boxes_dev  # noqa: F401
+from .voxel_map import VoxelMap, gather_boxes_dev, distance_transform_dev, distance_query_dev, DIST_NONE  # noqa: F401
 from . import path_search  # noqa: F401
 from .path_search import plan_path, plan_paths, PATH_EXACT, PATH_APPROXIMATE, PATH_INVALID_START  # noqa: F401
 from . import flatness  # noqa: F401
@@ -41,6 +41,9 @@ from .flatness import (FlatnessMap, flat_forward, flat_forward_dev, flat_backwar
 from . import avoid  # noqa: F401
 from .avoid import (AvoidOthers, make_avoid_penalty, minco_avoid_partial_grads_dev, minco_avoid_cost_grad_dev,  # noqa: F401
                     minco_avoid_cost_grad, neighbours_all, neighbours_from_pairs, upload_others, avoid_objective_dev)
+from . import obstacle  # noqa: F401
+from .obstacle import (make_obstacle_penalty, minco_obstacle_partial_grads_dev, minco_obstacle_cost_grad_dev,  # noqa: F401
+                       minco_obstacle_cost_grad, obstacle_objective_dev)
 from . import time_net  # noqa: F401
 from .time_net import TimeAllocNet  # noqa: F401
 from . import learning_planner  # noqa: F401

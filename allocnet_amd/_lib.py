@@ -133,6 +133,10 @@ PROTOTYPES = {
                              c_double] + [c_void_p] * 4),
     "anet_minco_avoid_partial_grads_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                                    c_int, c_int64, c_int64] + [c_void_p] * 5 + [c_int] + [c_void_p] * 5),
+    "anet_voxel_distance_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "anet_voxel_distance_query_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "anet_minco_obstacle_partial_grads_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                                      c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "anet_voxel_path_workspace": (c_int64, [c_void_p, c_int64]),
     "anet_voxel_path_field_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                           c_void_p]),
@@ -250,6 +254,13 @@ class AvoidPenalty(ctypes.Structure):
     """struct anet_avoid_penalty (include/allocnet_amd.h)."""
     _fields_ = [("w", c_double), ("smooth_mu", c_double), ("min_dist", c_double), ("z_scale", c_double), ("res", ctypes.c_int32)]
 
+
+class ObstaclePenalty(ctypes.Structure):
+    """struct anet_obstacle_penalty (include/allocnet_amd.h)."""
+    _fields_ = [("w", c_double), ("smooth_mu", c_double), ("clearance", c_double), ("res", ctypes.c_int32)]
+
+
+ANET_DIST_NONE = 2 ** 31 - 1
 
 _lib = None
 

@@ -20,6 +20,7 @@
 //   api_clearance.hip  exact clearance of trajectories to obstacle points
 //   api_separation.hip exact minimum separation between pairs of trajectories
 //   api_avoid.hip      trajectory-avoidance penalty of the MINCO objective against neighbours of another set of trajectories
+//   api_distance.hip   exact distance field of the voxel map, its query, the obstacle penalty of the MINCO objective
 //   piece_grad_unit.hip, qp_ipm_fuse_unit.hip: kernels scheduled for ILP, reached through launch functions
 // Only what two or more units use is here.  Nothing here is exported: the library's dynamic symbols stay the anet_* entry
 // points (and the kernels).

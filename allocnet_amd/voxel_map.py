@@ -8,12 +8,13 @@ import ctypes
 
 import numpy as np
 
-from ._lib import VoxelGrid
+from ._lib import VoxelGrid, ANET_DIST_NONE
 from .context import default_context
 
 Unoccupied = 0
 Occupied = 1
 Dilated = 2
+DIST_NONE = ANET_DIST_NONE    # the distance field's value for a minimum over nothing (+: no blocked voxel, -: no free one)
 
 
 def _vp(t):
@@ -46,6 +47,7 @@ class VoxelMap:
         self._ids = torch.zeros(0, dtype=torch.int32, device=self.device)
         self._count = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._surf_pts = None
+        self._dist = {}                     # the distance fields, per `walls`; dropped by whatever changes the voxel bytes
         # voxel_map.hpp's derived members: oc = o + 0.5 scale, stepScale = (1 / step) scale (numpy does not fuse)
         self._step = np.array([1, self._size[0], self._size[0] * self._size[1]], dtype=np.int64)
         self._oc = self._o + 0.5 * self._scale
@@ -70,7 +72,8 @@ class VoxelMap:
 
     @property
     def voxels_dev(self):
-        """The device voxel bytes (uint8, one per voxel, x fastest); writes through it bypass the map's bookkeeping."""
+        """The device voxel bytes (uint8, one per voxel, x fastest); writes through it bypass the map's bookkeeping (a cached
+        distance field does not see them: distance_field(refresh=True))."""
         return self._vox
 
     @property
@@ -98,6 +101,7 @@ class VoxelMap:
             ids = t[:, :3].to(device=self.device, dtype=torch.int64).clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous()
             self.ctx.check(self.ctx.lib.anet_voxel_set_occupied_ids_dev(self.ctx.handle, ctypes.byref(self._grid), _vp(self._vox),
                                                                         _vp(ids), ids.shape[0], self._stream()))
+            self._dist.clear()
             return
         if t.dtype not in (torch.float32, torch.float64):
             t = t.to(torch.float64)
@@ -117,6 +121,7 @@ class VoxelMap:
     def _scatter(self, t, n, stride, f64):
         self.ctx.check(self.ctx.lib.anet_voxel_set_occupied_dev(self.ctx.handle, ctypes.byref(self._grid), _vp(self._vox), _vp(t),
                                                                 int(n), int(stride), int(f64), self._stream()))
+        self._dist.clear()
 
     # ---- dilation and surface ---------------------------------------------------------------------
     def dilate(self, r):
@@ -130,6 +135,7 @@ class VoxelMap:
             self._work = torch.empty(self._ws_bytes, dtype=torch.uint8, device=self.device)
         lib, h, g, st = self.ctx.lib, self.ctx.handle, ctypes.byref(self._grid), self._stream()
         self.ctx.check(lib.anet_voxel_dilate_dev(h, g, _vp(self._vox), r, _vp(self._work), st))
+        self._dist.clear()
         cap = max(self._ids.numel(), 1024)
         ids = torch.empty(cap, dtype=torch.int32, device=self.device)
         self.ctx.check(lib.anet_voxel_surface_dev(h, g, _vp(self._work), cap, _vp(ids), _vp(self._count), st))
@@ -181,6 +187,32 @@ class VoxelMap:
         res = out.cpu().numpy().astype(bool)
         return bool(res[0]) if single else res
 
+    # ---- the distance field ---------------------------------------------------------------------------
+    def distance_field(self, walls=True, refresh=False):
+        """The exact signed squared distance field of the map (anet_voxel_distance_dev): int32 CUDA tensor, one value per voxel
+        in the layout of the bytes, + to the nearest blocked voxel for a free one, - to the nearest free voxel for a blocked one,
+        in voxel units; walls: the outside of the map counts as blocked.  Cached per `walls` and dropped by setOccupied,
+        setOccupiedCloud and dilate; writes through voxels_dev bypass the cache: refresh=True computes it again."""
+        key = bool(walls)
+        if refresh or key not in self._dist:
+            self._dist[key] = distance_transform_dev(self, self._vox, key, out=self._dist.get(key))
+        return self._dist[key]
+
+    def getDistance(self, pos, grad=False, walls=True):
+        """The distance in metres from pos to the nearest obstacle (negative inside one): the trilinear interpolant of the field's
+        centre values (anet_voxel_distance_query_dev), constant beyond the outermost voxel centres.  One 3-vector -> float, (n, 3)
+        -> (n,) numpy; grad=True returns (dist, gradient) with the gradient (3,) / (n, 3)."""
+        import torch
+        single = np.ndim(pos) == 1 if not isinstance(pos, torch.Tensor) else pos.dim() == 1
+        t = pos if isinstance(pos, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pos, dtype=np.float64))
+        t = t.to(device=self.device, dtype=torch.float64).reshape(-1, 3).contiguous()
+        d, g = distance_query_dev(self, self.distance_field(walls), t, grad=grad)
+        d = d.cpu().numpy()
+        if not grad:
+            return float(d[0]) if single else d
+        g = g.cpu().numpy()
+        return (float(d[0]), g[0]) if single else (d, g)
+
     def posI2D(self, id):
         """id * scale + oc (a different rounding from the surface's id * stepScale + oc, as in the reference)."""
         return np.asarray(id).astype(np.float64) * self._scale + self._oc
@@ -231,3 +263,52 @@ def gather_boxes_dev(bd, points, ctx=None):
     if K and counts.max() > 0:
         ctx.check(ctx.lib.anet_voxel_gather_boxes_dev(ctx.handle, K, _vp(bd), pp, n, Np, _vp(work), _vp(pc), _vp(cnt), st))
     return pc, counts
+
+
+def _grid_of(vm_or_grid):
+    """(VoxelGrid, context or None) of a VoxelMap or a VoxelGrid."""
+    if isinstance(vm_or_grid, VoxelMap):
+        return vm_or_grid._grid, vm_or_grid.ctx
+    if not isinstance(vm_or_grid, VoxelGrid):
+        raise TypeError("a VoxelMap or a VoxelGrid expected")
+    return vm_or_grid, None
+
+
+def distance_transform_dev(vm_or_grid, voxels, walls=True, out=None, stream=None, ctx=None):
+    """anet_voxel_distance_dev on tensors: voxels uint8 CUDA (n_voxels,), -> the int32 field (n_voxels,) (`out` when given).
+    Asynchronous on the current stream."""
+    import torch
+    grid, own = _grid_of(vm_or_grid)
+    ctx = ctx or own or default_context(voxels.device.index or 0)
+    n = int(grid.size[0]) * int(grid.size[1]) * int(grid.size[2])
+    if voxels.dtype != torch.uint8 or voxels.numel() != n or not voxels.is_contiguous() or not voxels.is_cuda:
+        raise ValueError("distance_transform_dev: voxels must be a contiguous uint8 CUDA tensor with one byte per voxel")
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=voxels.device)
+    elif out.dtype != torch.int32 or out.numel() != n or not out.is_contiguous() or out.device != voxels.device:
+        raise ValueError("distance_transform_dev: out must be a contiguous int32 tensor with one value per voxel, on the device of voxels")
+    st = ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(voxels.device).cuda_stream)
+    ctx.check(ctx.lib.anet_voxel_distance_dev(ctx.handle, ctypes.byref(grid), _vp(voxels), 1 if walls else 0, _vp(out), st))
+    return out
+
+
+def distance_query_dev(vm_or_grid, sd2, pos, grad=True, stream=None, ctx=None):
+    """anet_voxel_distance_query_dev on tensors: sd2 the int32 field, pos (n, 3) float64 CUDA -> (dist (n,), grad (n, 3) or None)."""
+    import torch
+    grid, own = _grid_of(vm_or_grid)
+    ctx = ctx or own or default_context(sd2.device.index or 0)
+    if sd2.dtype != torch.int32 or sd2.numel() != int(grid.size[0]) * int(grid.size[1]) * int(grid.size[2]) or \
+            not sd2.is_contiguous():
+        raise ValueError("distance_query_dev: sd2 must be the contiguous int32 field of this grid")
+    if pos.dtype != torch.float64 or pos.dim() != 2 or pos.shape[1] != 3:
+        raise ValueError("distance_query_dev: pos must be (n, 3) float64")
+    if not (sd2.is_cuda and pos.is_cuda) or sd2.device != pos.device:
+        raise ValueError("distance_query_dev: sd2 and pos must be CUDA tensors on one device")
+    pos = pos.contiguous()
+    n = pos.shape[0]
+    dist = torch.empty(n, dtype=torch.float64, device=pos.device)
+    g = torch.empty((n, 3), dtype=torch.float64, device=pos.device) if grad else None
+    st = ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(pos.device).cuda_stream)
+    ctx.check(ctx.lib.anet_voxel_distance_query_dev(ctx.handle, ctypes.byref(grid), _vp(sd2), _vp(pos) if n else None, n,
+                                                    _vp(dist) if n else None, _vp(g) if (grad and n) else None, st))
+    return dist, g

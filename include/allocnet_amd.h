@@ -966,6 +966,58 @@ int anet_minco_avoid_partial_grads_dev(anet_ctx *ctx, const anet_avoid_penalty *
                                        int accumulate, double *gdC, double *gdT, double *piece_cost /* may be NULL */,
                                        double *gd_t0 /* [ld], may be NULL */, void *stream);
 
+/* ---- exact distance field of the voxel map, its query and its penalty of the MINCO objective (no counterpart in the reference) ----
+ * The field: sd2 [n_voxels] int32 in the layout of the voxel bytes is the SIGNED SQUARED Euclidean distance in voxel units, an
+ * exact integer.  blocked(v) <=> voxels[v] != 0, the predicate of anet_voxel_query_dev (dilated voxels count):
+ *     free v      sd2[v] = + min over blocked u of |v - u|^2      (index coordinates)
+ *     blocked v   sd2[v] = - min over free u of |v - u|^2
+ * walls != 0: the voxels outside the map count as blocked too, as query answers 1 there, so the candidates of a free voxel include
+ * min(x + 1, sx - x, y + 1, sy - y, z + 1, sz - z)^2; walls never count as free.  A minimum over an empty set gives
+ * +ANET_DIST_NONE / -ANET_DIST_NONE; such a map is uniformly one sentinel, and with walls +ANET_DIST_NONE cannot occur.
+ * Every axis <= 4096 voxels, so |sd2| <= 3 * 4096^2 < 2^31; a longer axis is ANET_ERR_UNSUPPORTED, a bad grid or a NULL pointer
+ * ANET_ERR_INVALID.  Asynchronous on `stream`, deterministic, no atomics, no workspace: sd2 is the only memory written.        */
+#define ANET_DIST_NONE INT32_MAX
+int anet_voxel_distance_dev(anet_ctx *ctx, const anet_voxel_grid *grid, const uint8_t *voxels, int walls, int32_t *sd2 /* [n_voxels] */,
+                            void *stream);
+/* The query: the centre value of voxel v is D(v) = scale * sgn(sd2[v]) * sqrt(|sd2[v]|) in double (+-inf for a sentinel), the centres
+ * are oc + index * scale with oc = origin + 0.5 * scale.  Per axis
+ *     u = (p - oc) / scale (a subtraction and an IEEE division, not contracted),  i0 = clamp(floor(u), 0, max(size - 2, 0)),
+ *     f = clamp(u - i0, 0, 1),  i1 = min(i0 + 1, size - 1)
+ * dist [n] is the trilinear interpolant of D at the eight corners; grad [n][3] (may be NULL) is the gradient of that interpolant
+ * inside its cell divided by scale (an IEEE division; the interpolant's own sums may be fused), and 0 where f was clamped or size == 1.  BEYOND THE OUTERMOST CENTRES THE FIELD
+ * THEREFORE CONTINUES AS A CONSTANT: a curve is kept inside the map by a corridor, or by `walls` with a clearance above one voxel.
+ * Across a lattice plane the gradient jumps.  A sentinel corner (a uniform map): dist = +-inf, grad = 0.  A non-finite coordinate
+ * gives NaN in dist and grad of that point only.  pos [n][3]; n == 0 returns ANET_OK.                                           */
+int anet_voxel_distance_query_dev(anet_ctx *ctx, const anet_voxel_grid *grid, const int32_t *sd2, const double *pos /* [n][3] */,
+                                  int64_t n, double *dist /* [n] */, double *grad /* [n][3], may be NULL */, void *stream);
+/* The penalty: what anet_traj_voxel_hit and getClearance find, this term removes.  Layouts, orders 2 / 3 / 4 and ANET_MAX_PIECES are
+ * those of anet_minco_avoid_partial_grads_dev; the sum is the left Riemann sum of J_pen, J_flat and J_avoid.  Sample j < res of
+ * piece i: sigma = (double)j / (double)res, tau = sigma * T_i, one rounding each.  With d and grad d from the query above at
+ * p_i(tau):
+ *     Phi = w smoothedL1_mu(clearance - d)
+ *     J_obs(b)        = sum_i (T_i / res) sum_(j < res) Phi
+ *     F               = -w phi' grad d
+ *     dJ/dc[i][ax][k] = (T_i/res) sum_j F_ax tau^k
+ *     dJ/dT_i         = (1/res) sum_j Phi + (T_i/res) sum_j sigma (F . v_i(tau))
+ * There is no t0: the map does not move.  gdC, gdT, piece_cost (may be NULL): the shapes of anet_minco_partial_grads_dev.
+ * accumulate = 0: they are written; != 0: the kernel's complete share is added to the stored value with one unfused addition, bit
+ * for bit the sum of the two separate results.  Lanes in [batch, ld) are never touched.  No atomics, no workspace; the outputs of
+ * trajectory b have the same bits alone or among many, and at any ld.  Exact zeros when every term is inactive, a map of
+ * +ANET_DIST_NONE included.  All outputs of b, and only of b, are NaN when a duration of b is not finite or <= 0, a sample position
+ * of b is not finite, or d = -inf (the all-blocked map).  Orders 2, 3, 4 (ANET_ERR_UNSUPPORTED otherwise); ANET_ERR_INVALID: a NULL
+ * pointer other than piece_cost, ld < batch, a piece count outside [1, ANET_MAX_PIECES], a bad grid, a penalty outside the ranges
+ * below.  batch == 0 returns ANET_OK and touches nothing.                                                                      */
+typedef struct anet_obstacle_penalty {
+  double w;         /* weight, >= 0 */
+  double smooth_mu; /* smoothedL1 mu in m, > 0 */
+  double clearance; /* the distance to keep in m, finite */
+  int32_t res;      /* samples per piece, >= 1 */
+} anet_obstacle_penalty;
+int anet_minco_obstacle_partial_grads_dev(anet_ctx *ctx, const anet_obstacle_penalty *pen, int s, int n_pieces, int64_t batch,
+                                          int64_t ld, const double *coeffs, const double *T, const anet_voxel_grid *grid,
+                                          const int32_t *sd2, int accumulate, double *gdC, double *gdT,
+                                          double *piece_cost /* may be NULL */, void *stream);
+
 /* ---- front-end route on the voxel map: sfc_gen::planPath ----------------------------------------------------------------
  * A collision-free polyline from s to g and its length, by a shortest-path field on the grid, a walk back along it and a
  * line-of-sight shortcut; exact and deterministic (no time budget).  box = {lb[3], hb[3]} (host array), the planner's

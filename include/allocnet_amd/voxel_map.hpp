@@ -68,7 +68,7 @@ class VoxelMap {
     return *this;
   }
   ~VoxelMap() {
-    for (uint8_t *p : {vox_, work_, count_, ids_, pts_}) anet_dev_free((double *)p);
+    for (uint8_t *p : {vox_, work_, count_, ids_, pts_, dist_[0], dist_[1]}) anet_dev_free((double *)p);
   }
 
   Vec3i getSize() const { return Vec3i(g_.size[0], g_.size[1], g_.size[2]); }
@@ -104,6 +104,7 @@ class VoxelMap {
     anet_dev_free((double *)d);
     ctx.check(rc);
     stale_ = true;
+    dist_valid_[0] = dist_valid_[1] = false;
   }
 
   void dilate(const int &r) {
@@ -128,6 +129,7 @@ class VoxelMap {
     nsurf_ = n;
     pts_dev_valid_ = pts_host_valid_ = false;
     stale_ = true;
+    dist_valid_[0] = dist_valid_[1] = false;
   }
 
   template <class V3i, class V3d>
@@ -181,6 +183,36 @@ class VoxelMap {
                  (int)((pos(2) - g_.origin[2]) / scale_));
   }
 
+  // The exact distance field (anet_voxel_distance_dev): DEVICE int32 [voxels], the signed squared distance in voxel units, + to the
+  // nearest blocked voxel for a free one, - to the nearest free voxel for a blocked one; walls: the outside counts as blocked.
+  // Computed on first use after a change of the map, one per value of `walls`.
+  const int32_t *distanceField(bool walls = true) const {
+    flush();
+    const int k = walls ? 1 : 0;
+    if (dist_valid_[k]) return (const int32_t *)dist_[k];
+    anet::Context &ctx = anet::Context::thread_default();
+    if (!dist_[k]) dist_[k] = alloc_bytes(ctx, (size_t)voxNum_ * 4);
+    ctx.check(anet_voxel_distance_dev(ctx.get(), &g_, vox_, k, (int32_t *)dist_[k], anet_stream(ctx.get())));
+    dist_valid_[k] = true;
+    return (const int32_t *)dist_[k];
+  }
+  // The distance in metres from p to the nearest obstacle, negative inside one: the trilinear interpolant of the field's centre
+  // values (anet_voxel_distance_query_dev; constant beyond the outermost voxel centres); grad: its gradient.
+  template <class V>
+  double getDistance(const V &p, bool walls = true) const {
+    double d = 0.0, g[3];
+    distance_one(p, walls, d, g);
+    return d;
+  }
+  // (grad: anything with assignable (i) access; a bool lvalue is `walls` of the overload above, never a gradient)
+  template <class V, class G, class = typename std::enable_if<!std::is_same<typename std::remove_cv<G>::type, bool>::value>::type>
+  double getDistance(const V &p, G &grad, bool walls = true) const {
+    double d = 0.0, g[3];
+    distance_one(p, walls, d, g);
+    for (int c = 0; c < 3; ++c) grad(c) = g[c];
+    return d;
+  }
+
   // device side, for convexCover and other kernels: the voxel bytes, the surface's ascending ids and points [n][3]
   const anet_voxel_grid &grid() const { return g_; }
   const uint8_t *voxels_dev() const {
@@ -217,6 +249,7 @@ class VoxelMap {
     pend_.clear();
     pend_ids_.clear();
     stale_ = true;
+    dist_valid_[0] = dist_valid_[1] = false;
   }
 
  private:
@@ -224,7 +257,8 @@ class VoxelMap {
   double scale_ = 0.0;
   int64_t voxNum_ = 0;
   uint8_t *vox_ = nullptr, *work_ = nullptr, *count_ = nullptr, *ids_ = nullptr;
-  mutable uint8_t *pts_ = nullptr;
+  mutable uint8_t *pts_ = nullptr, *dist_[2] = {nullptr, nullptr};
+  mutable bool dist_valid_[2] = {false, false};
   int64_t ids_cap_ = 0, nsurf_ = 0;
   mutable int64_t pts_cap_ = 0;
   mutable bool pts_dev_valid_ = false, pts_host_valid_ = false, stale_ = false;
@@ -244,6 +278,10 @@ class VoxelMap {
     std::swap(pts_dev_valid_, o.pts_dev_valid_); std::swap(pts_host_valid_, o.pts_host_valid_); std::swap(stale_, o.stale_);
     pend_.swap(o.pend_); pend_ids_.swap(o.pend_ids_); pts_host_.swap(o.pts_host_);
     mirror_.swap(o.mirror_);
+    for (int k = 0; k < 2; ++k) {
+      std::swap(dist_[k], o.dist_[k]);
+      std::swap(dist_valid_[k], o.dist_valid_[k]);
+    }
   }
   template <class V>
   void set_one(const V &pos, std::false_type) {
@@ -253,6 +291,21 @@ class VoxelMap {
   template <class V>
   void set_one(const V &id, std::true_type) {  // the index itself; the kernel drops it when it is out of bounds
     pend_ids_.push_back((int32_t)id(0)); pend_ids_.push_back((int32_t)id(1)); pend_ids_.push_back((int32_t)id(2));
+  }
+  template <class V>
+  void distance_one(const V &p, bool walls, double &d, double (&g)[3]) const {
+    const int32_t *sd2 = distanceField(walls);
+    anet::Context &ctx = anet::Context::thread_default();
+    double *buf = nullptr;  // pos [3], dist [1], grad [3]
+    ctx.check(anet_dev_alloc(ctx.get(), 7, &buf));
+    double h[7] = {(double)p(0), (double)p(1), (double)p(2), 0.0, 0.0, 0.0, 0.0};
+    int rc = anet_dev_upload(ctx.get(), buf, h, 3);
+    if (rc == ANET_OK) rc = anet_voxel_distance_query_dev(ctx.get(), &g_, sd2, buf, 1, buf + 3, buf + 4, anet_stream(ctx.get()));
+    if (rc == ANET_OK) rc = anet_dev_download(ctx.get(), h, buf, 7);
+    anet_dev_free(buf);
+    ctx.check(rc);
+    d = h[3];
+    for (int c = 0; c < 3; ++c) g[c] = h[4 + c];
   }
   void refresh() const {
     flush();
