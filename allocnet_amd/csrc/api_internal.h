@@ -74,13 +74,14 @@ struct anet_ctx {
     hipEvent_t ready;
   };
   std::vector<BasisTable> tabs;
-  // tables of k_qp_ipm, one per (order, res, m34) ever used (csrc/qp_ipm.h k_qp_ipm_tables): same lifetime rules
+  // tables of k_qp_ipm, one per (order, res, m34, row form) ever used (csrc/qp_ipm.h k_qp_ipm_tables): same lifetime rules
   struct IpmTable {
     int s, res;
     double m34;
     double *d;
     hipStream_t built_on;
     hipEvent_t ready;
+    int control_points;  // 0: rows at samples, 1: rows on Bernstein control values (ANET_QP_ROWS_CONTROL_POINTS)
   };
   std::vector<IpmTable> ipm_tabs;
 };

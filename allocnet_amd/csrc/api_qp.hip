@@ -26,8 +26,14 @@ int anet_qp_assemble_dev(anet_ctx *ctx, int s, int n_pieces, int64_t batch, int 
                          double *Q, double *A, double *b, double *G, double *h, void *stream) {
   ANET_ON_DEVICE(ctx);
   if (s != 3 && s != 4) return fail(ctx, ANET_ERR_INVALID, "anet_qp_assemble: order must be 3 (jerk) or 4 (snap), qp_solver.hpp:61-83");
+  const int control_points = (row_order & ANET_QP_ROWS_CONTROL_POINTS) ? 1 : 0;
+  row_order &= ~ANET_QP_ROWS_CONTROL_POINTS;
   if (n_pieces < 1 || batch < 0 || res < 1 || M < 0 || (row_order != 0 && row_order != 1))
     return fail(ctx, ANET_ERR_INVALID, "anet_qp_assemble: bad argument");
+  if (control_points && res % (2 * s) != 0)
+    return fail(ctx, ANET_ERR_INVALID, "anet_qp_assemble: control-point rows need res = k * 2 * order (k Bernstein segments per piece)");
+  if (control_points && float_time)
+    return fail(ctx, ANET_ERR_UNSUPPORTED, "anet_qp_assemble: control-point rows are assembled in double only (no float_time)");
   if (batch == 0) return ANET_OK;
   if (!state || !T || !rows || (M > 0 && !hpolys) || !Q || !A || !b || !G || !h)
     return fail(ctx, ANET_ERR_INVALID, "anet_qp_assemble: NULL pointer");
@@ -47,7 +53,7 @@ int anet_qp_assemble_dev(anet_ctx *ctx, int s, int n_pieces, int64_t batch, int 
       return fail(ctx, ANET_ERR_INVALID, "anet_qp_assemble: every trajectory of a batch needs the same total polytope row count");
   }
   anet::QpArgs a{state, T, hpolys, rows, Q, A, b, G, h, batch, dm.n, dm.m_e, dm.m_g, n_pieces, res, M,
-                 float_time ? 1 : 0, row_order, max_vel, max_acc, m34};
+                 float_time ? 1 : 0, row_order, max_vel, max_acc, m34, control_points};
   hipStream_t st = (hipStream_t)stream;
   const int64_t ne = dm.n * dm.n + dm.m_e * dm.n + dm.m_e, ng = dm.m_g * dm.n;
   const dim3 blk(256), g1((unsigned)((ne + 255) / 256), (unsigned)batch), g2((unsigned)((ng + 255) / 256), (unsigned)batch);
@@ -221,8 +227,17 @@ static int qp_solve_dev_impl(anet_ctx *ctx, int s, int n_pieces, int64_t batch, 
   if (!(st_.rho > 0) || !(st_.sigma > 0) || !(st_.alpha > 0 && st_.alpha < 2) || st_.max_iter < 1 ||
       st_.check_termination < 1 || st_.eps_abs < 0 || st_.eps_rel < 0 || st_.adaptive_rho_interval < 0)
     return fail(ctx, ANET_ERR_INVALID, "anet_qp_solve: bad settings");
+  // the row form rides on the method word (ANET_QP_ROWS_CONTROL_POINTS); every other unknown bit or value is refused
+  const int control_points = (st_.method & ANET_QP_ROWS_CONTROL_POINTS) ? 1 : 0;
+  st_.method &= ~ANET_QP_ROWS_CONTROL_POINTS;
   if (st_.method != ANET_QP_METHOD_ADMM && st_.method != ANET_QP_METHOD_INTERIOR_POINT)
     return fail(ctx, ANET_ERR_INVALID, "anet_qp_solve: unknown method");
+  if (control_points) {
+    if (res % (2 * s) != 0)
+      return fail(ctx, ANET_ERR_INVALID, "anet_qp_solve: control-point rows need res = k * 2 * order (k Bernstein segments per piece)");
+    if (st_.method != ANET_QP_METHOD_INTERIOR_POINT)
+      return fail(ctx, ANET_ERR_UNSUPPORTED, "anet_qp_solve: control-point rows need the interior-point method");
+  }
   const anet::QpSolveWs W = anet::qp_solve_ws(work, s, n_pieces, batch, res, M);
   if (st_.method == ANET_QP_METHOD_INTERIOR_POINT) {
     const size_t ldsb = qp_ipm_lds(s, n_pieces, res, M);
@@ -245,10 +260,10 @@ static int qp_solve_dev_impl(anet_ctx *ctx, int s, int n_pieces, int64_t batch, 
       hipLaunchKernelGGL(k_qp_mark_not_run, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, sti, batch, status, iters, obj);
       ANET_HIP(ctx, hipGetLastError());
     }
-    {  // the tables of (order, res, m34): built once, on the stream that first needs them
+    {  // the tables of (order, res, m34, row form): built once, on the stream that first needs them
       const double *tab = nullptr;
       for (auto &tb : ctx->ipm_tabs)
-        if (tb.s == s && tb.res == res && tb.m34 == m34) {
+        if (tb.s == s && tb.res == res && tb.m34 == m34 && tb.control_points == control_points) {
           if (tb.built_on != sti) ANET_HIP(ctx, hipStreamWaitEvent(sti, tb.ready, 0));
           tab = tb.d;
         }
@@ -256,15 +271,15 @@ static int qp_solve_dev_impl(anet_ctx *ctx, int s, int n_pieces, int64_t batch, 
         // (never freed before anet_destroy -- a launch on another stream may still read one: a caller that sweeps m34 or res over
         //  hundreds of values is told so instead of growing the context without bound)
         if (ctx->ipm_tabs.size() >= kMaxTablesPerContext)
-          return fail(ctx, ANET_ERR_UNSUPPORTED, "anet_qp_solve: more than 256 distinct (order, res, m34) on one context");
-        anet_ctx::IpmTable tb{s, res, m34, nullptr, sti, nullptr};
+          return fail(ctx, ANET_ERR_UNSUPPORTED, "anet_qp_solve: more than 256 distinct (order, res, m34, row form) on one context");
+        anet_ctx::IpmTable tb{s, res, m34, nullptr, sti, nullptr, control_points};
         const size_t need = (size_t)2 * (2 * s) * (2 * s) + (size_t)res * anet::ipm_ht_stride(2 * s);
         int rc_t = new_table(ctx, sizeof(double) * need, &tb.d, &tb.ready);
         if (rc_t) return rc_t;
         hipError_t e1 = hipMemsetAsync(tb.d, 0, sizeof(double) * need, sti);
         if (e1 == hipSuccess) {
-          if (s == 4) hipLaunchKernelGGL(anet::k_qp_ipm_tables<4>, dim3(1), dim3(256), 0, sti, tb.d, res, m34);
-          else hipLaunchKernelGGL(anet::k_qp_ipm_tables<3>, dim3(1), dim3(256), 0, sti, tb.d, res, m34);
+          if (s == 4) hipLaunchKernelGGL(anet::k_qp_ipm_tables<4>, dim3(1), dim3(256), 0, sti, tb.d, res, m34, control_points);
+          else hipLaunchKernelGGL(anet::k_qp_ipm_tables<3>, dim3(1), dim3(256), 0, sti, tb.d, res, m34, control_points);
           e1 = hipGetLastError();
         }
         if (e1 == hipSuccess) e1 = hipEventRecord(tb.ready, sti);

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "qp_control_points.h"
+
 namespace anet {
 
 // ------------------------------------------------------------------------------------------
@@ -15,6 +17,7 @@ struct QpArgs {
   int64_t B, n, me, mg;
   int N, res, M, float_time, row_order;
   double vmax, amax, m34;
+  int control_points;  // 1: G holds the rows on Bernstein control values (qp_control_points.h) instead of at samples; double only
 };
 
 // Row d (0 = p, 1 = v, 2 = a, 3 = j) of the monomial basis at t, column `col` (highest power first),
@@ -106,6 +109,22 @@ __global__ void __launch_bounds__(256) k_qp_eq_obj(QpArgs a) {
   }
 }
 
+// Control-point row form: the entry of column `col` (power k = D - 1 - col of REAL time) in the row "elevated control value r of
+// derivative d on segment q of K" of a piece of duration T.  The functional is the normalised one of qp_control_points.h applied to
+// tau^k; t = T tau puts T^(k - d) in front.
+template <int S>
+__device__ inline double control_point_entry(double T, int d, int q, int K, int r, int col) {
+  constexpr int D = 2 * S;
+  const int k = D - 1 - col;
+  if (k < d) return 0.0;
+  double c[D], beta[D];
+  for (int e = 0; e < D; ++e) c[e] = (e == k) ? 1.0 : 0.0;
+  qp_control_values<D>(c, d, q, K, beta);
+  double v = beta[r];
+  for (int e = 0; e < k - d; ++e) v *= T;
+  return v;
+}
+
 // [G | h]: one thread per element of G, the thread of column 0 also writes h.
 template <int S, class F>
 __global__ void __launch_bounds__(256) k_qp_ineq(QpArgs a) {
@@ -155,12 +174,17 @@ __global__ void __launch_bounds__(256) k_qp_ineq(QpArgs a) {
   const F step = seg_time<S, F>(a, b, i) / (F)res;
   const F t = (j == 0) ? (F)0 : step * (F)j;
   const int64_t c0 = (int64_t)i * 3 * D;
+  // the row's functional on one axis' coefficients: derivative d at the sample, or control value j % D of segment j / D
+  auto basis = [&](int d, int col) -> double {
+    if (a.control_points) return control_point_entry<S>(a.T[b * N + i], d, j / D, res / D, j % D, col);
+    return basis_entry<S, F>(t, d, col);
+  };
   double v = 0.0, hv = 0.0;
   if (!box) {
     const double *hp = a.hpolys + ((b * N + i) * a.M + q) * 4;
     if (c >= c0 && c < c0 + 3 * D) {
       const int ax = (int)((c - c0) / D);
-      v = hp[ax] * basis_entry<S, F>(t, 0, (int)((c - c0) % D));
+      v = hp[ax] * basis(0, (int)((c - c0) % D));
     }
     hv = hp[3];
   } else {
@@ -168,7 +192,7 @@ __global__ void __launch_bounds__(256) k_qp_ineq(QpArgs a) {
     const int ax = q / 4, w = q % 4;
     const int64_t ca = c0 + ax * D;
     if (c >= ca && c < ca + D) {
-      const double be = basis_entry<S, F>(t, 1 + (w & 1), (int)(c - ca));
+      const double be = basis(1 + (w & 1), (int)(c - ca));
       v = (w < 2) ? be : -be;
     }
     hv = (w & 1) ? a.amax : a.vmax;

@@ -10,7 +10,9 @@
 //    the shape the MINCO solve already uses (minco_core.h).
 //  * piece i sees u_i = [y_i ; (T_i/T_i+1)^d y_i+1]; every row of the QP is a Hermite basis function (or a
 //    derivative) at tau_j = j/res contracted with a 3-vector, so A'WA is assembled from per-sample 3x3 /
-//    3-vector weights and one table of 3*res*2s numbers; Q, A, G are never formed.
+//    3-vector weights and one table of 3*res*2s numbers; Q, A, G are never formed.  (That table is all a row is to this
+//    kernel: with ANET_QP_ROWS_CONTROL_POINTS its entries are elevated Bernstein control values of segments of the piece
+//    instead of values at tau_j -- k_qp_ipm_tables, qp_control_points.h -- and "sample j" below reads "group j".)
 //  * Mehrotra predictor-corrector; the two solves of a step share one block Cholesky.  What is sequential in a step
 //    is kept short and what is idle is given work (round 3):
 //      - TWISTED factorisation: the chain of knots is eliminated from both ends towards the middle by two waves at
@@ -39,6 +41,7 @@
 #include "wave_ops.h"  // wave_sum, wave_min_f64, pair_sum
 #include "qp_admm.h"    // qblk1, fallf
 #include "workspace_constants.h"  // kIpmContScalars
+#include "qp_control_points.h"    // qp_control_values
 
 namespace anet {
 
@@ -129,10 +132,13 @@ inline size_t qp_ipm_lds_bytes(int N, int R, int M) {
 
 // The tables of k_qp_ipm that depend on (order, samples per piece, m34) only -- Hm = inverse of the Hermite collocation matrix
 // (Gauss-Jordan on ONE thread), the basis rows ht at tau_j, the cost block Hobj in Hermite coordinates -- built ONCE per context
-// and (order, res, m34) by this one-workgroup kernel and copied into LDS by every solve (0.7 of a Newton step of every workgroup
+// and (order, res, m34, row form) by this one-workgroup kernel and copied into LDS by every solve (0.7 of a Newton step of every workgroup
 // went into rebuilding them: 98 k of the lone 8-piece problem's 1.55 M cycles).  Layout: Hm [D][D] | Hobj [D][D] | ht [R][3 D + 1].
+// control_points != 0 (R = K D, checked by the host): row j = q D + r of ht is not "derivative d at tau_j" but "elevated Bernstein
+// control value r of derivative d on segment q of K" (qp_control_points.h) of each Hermite basis function -- the only place the
+// two row forms differ: every phase of k_qp_ipm reads ht as a table of linear functionals and never asks where tau_j is.
 template <int S>
-__global__ void __launch_bounds__(256) k_qp_ipm_tables(double *out, int R, double m34) {
+__global__ void __launch_bounds__(256) k_qp_ipm_tables(double *out, int R, double m34, int control_points) {
   constexpr int D = 2 * S, HS = ipm_ht_stride(D);
   const int tid = threadIdx.x, nt = blockDim.x;
   __shared__ double E[2 * D * D], Hm[D * D];
@@ -166,7 +172,18 @@ __global__ void __launch_bounds__(256) k_qp_ipm_tables(double *out, int R, doubl
       for (int c = 0; c < D; ++c) Hm[r * D + c] = E[r * W + D + c];  // Hm[col][m]
   }
   __syncthreads();
-  for (int e = tid; e < R * 3 * D; e += nt) {
+  if (control_points) {
+    const int K = R / D;
+    for (int e = tid; e < K * 3 * D; e += nt) {  // one thread per (segment, derivative, basis function): its D control values
+      const int q = e / (3 * D), d = (e / D) % 3, m = e % D;
+      double c[D], beta[D];
+      for (int k = 0; k < D; ++k) c[k] = Hm[(D - 1 - k) * D + m];
+      qp_control_values<D>(c, d, q, K, beta);
+      for (int r = 0; r < D; ++r) ht[(size_t)(q * D + r) * HS + d * D + m] = beta[r];
+    }
+  }
+  const int n_sampled = control_points ? 0 : R * 3 * D;
+  for (int e = tid; e < n_sampled; e += nt) {
     const int j = e / (3 * D), d = (e / D) % 3, m = e % D;  // stored at ht[j * HS + d * D + m]
     const double tau = (double)j / (double)R;
     double v = 0.0;

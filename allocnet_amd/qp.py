@@ -10,6 +10,27 @@ from ._lib import QpDims
 ORDER_CPP = 0      # per sample: polytope rows then 12 box rows (qp_solver.hpp:258-294)
 ORDER_PYTHON = 1   # all corridor rows (G1,h1), then all box rows (G2,h2) (min_traj_opt.py:535-613)
 
+# ANET_QP_ROWS_CONTROL_POINTS: OR-ed into QpSettings.method (the solves) or into row_order (the assembly).  The corridor and box
+# rows are then held on Bernstein control values -- for every t of every piece -- instead of at samples: res = segments * 2 * order,
+# group j = q * 2 * order + r is control value r of segment q.  Interior point only, double only.
+QP_ROWS_CONTROL_POINTS = 0x100
+ROW_FORMS = {"samples": 0, "control_points": QP_ROWS_CONTROL_POINTS}
+
+
+def _row_form_bit(rows):
+    if rows is None:
+        return 0
+    if rows not in ROW_FORMS:
+        raise ValueError("rows must be 'samples' or 'control_points'")
+    return ROW_FORMS[rows]
+
+
+def control_point_res(order, segments=1):
+    """The `res` of the control-point row form: `segments` Bernstein segments per piece, 2 * order control values each."""
+    if order not in (3, 4) or int(segments) < 1:
+        raise ValueError("order must be 3 or 4 and segments >= 1")
+    return int(segments) * 2 * int(order)
+
 
 def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
@@ -26,15 +47,18 @@ def qp_dims(order, rows, res, ctx=None):
 
 
 def qp_assemble(order, iniPVA, finPVA, hPolys, times, res=20, max_vel=4.0, max_acc=6.0, m34=1400.0,
-                float_time=False, row_order=ORDER_CPP, ctx=None):
+                float_time=False, row_order=ORDER_CPP, ctx=None, rows="samples"):
     """Batched QP assembly.
     iniPVA, finPVA : (B,3,3) row = axis, cols p,v,a          (learning_planning.cpp:150-151)
     hPolys         : (B,N,M,4) rows (a,b), a.x <= b, zero rows = padding; or a list (one trajectory)
                      of N arrays (m_i,4) like the reference's std::vector<Eigen::MatrixX4d>
     times          : (B,N)
+    rows           : "samples" (the reference's form) or "control_points" (res = control_point_res(order, segments); G and h
+                     hold the rows on Bernstein control values, Q, A and b are the same; not with float_time)
     Returns Q (B,n,n), A (B,me,n), b (B,me), G (B,mg,n), h (B,mg).
     Defaults: MaxVelBox/MaxAccBox/ConstRes of config/planner.yaml:17-21."""
     ctx = ctx or default_context()
+    form_bit = _row_form_bit(rows)
     single = isinstance(hPolys, (list, tuple))
     if single:
         N = len(hPolys)
@@ -63,7 +87,7 @@ def qp_assemble(order, iniPVA, finPVA, hPolys, times, res=20, max_vel=4.0, max_a
     Q = np.empty((B, n, n)); A = np.empty((B, me, n)); b = np.empty((B, me)); G = np.empty((B, mg, n)); h = np.empty((B, mg))
     hp = np.ascontiguousarray(hp); rows = np.ascontiguousarray(rows)
     ctx.check(ctx.lib.anet_qp_assemble(ctx.handle, int(order), N, B, int(res), M, float(max_vel), float(max_acc),
-                                       float(m34), int(bool(float_time)), int(row_order), _p(state), _p(T), _p(hp),
+                                       float(m34), int(bool(float_time)), int(row_order) | form_bit, _p(state), _p(T), _p(hp),
                                        _p(rows), _p(Q), _p(A), _p(b), _p(G), _p(h)))
     if single:
         return Q[0], A[0], b[0], G[0], h[0]
@@ -77,10 +101,10 @@ QP_METHOD_ADMM = 0             # OSQP's algorithm and settings (opt-in)
 QP_METHOD_INTERIOR_POINT = 1   # primal-dual interior point in Hermite node coordinates (csrc/qp_ipm.h): the default
 
 
-def qp_settings(**over):
+def qp_settings(rows=None, **over):
     """anet_qp_default_settings: OSQP's default tolerances and iteration parameters as the reference uses them (it never
     overrides any: qp_solver.hpp:299-302, layers.py:79), method = QP_METHOD_INTERIOR_POINT; method=QP_METHOD_ADMM
-    selects OSQP's own iteration."""
+    selects OSQP's own iteration.  rows="control_points" sets QP_ROWS_CONTROL_POINTS in `method` (rows="samples" clears it)."""
     from ._lib import QpSettings, load
     s = QpSettings()
     load().anet_qp_default_settings(ctypes.byref(s))
@@ -88,16 +112,31 @@ def qp_settings(**over):
         if not hasattr(s, k):
             raise AttributeError(k)
         setattr(s, k, v)
+    if rows is not None:
+        s.method = (s.method & ~QP_ROWS_CONTROL_POINTS) | _row_form_bit(rows)
     return s
 
 
+def _with_rows(settings, rows):
+    """`settings` (or the defaults) with the row form `rows` in its method word; rows=None leaves `settings` as given."""
+    if rows is None:
+        return settings
+    out = qp_settings()
+    if settings is not None:
+        ctypes.memmove(ctypes.byref(out), ctypes.byref(settings), ctypes.sizeof(out))
+    out.method = (out.method & ~QP_ROWS_CONTROL_POINTS) | _row_form_bit(rows)
+    return out
+
+
 def qp_solve(order, iniPVA, finPVA, hPolys, times, res=20, max_vel=4.0, max_acc=6.0, m34=1400.0,
-             settings=None, time_grad=False, ctx=None):
+             settings=None, time_grad=False, ctx=None, rows=None):
     """Batched QPSolver::solve.  iniPVA/finPVA (B,3,3); hPolys (B,N,M,4) rows a.x <= b (zero rows =
     padding); times (B,N).  Returns dict(coeffs (B,N,3,2s), obj (B,), status, iters, residuals (B,2));
     with time_grad=True also grad_T (B,N) = d(obj)/d(times), the derivative of the optimal cost through
-    the inequality QP (anet_qp_solve_time_grad: envelope theorem on the solver's multipliers)."""
+    the inequality QP (anet_qp_solve_time_grad: envelope theorem on the solver's multipliers).
+    rows: None (as `settings` says), "samples" or "control_points" (res = control_point_res(order, segments))."""
     ctx = ctx or default_context()
+    settings = _with_rows(settings, rows)
     hp = np.ascontiguousarray(hPolys, dtype=np.float64)
     B, N, M, _ = hp.shape
     state = np.ascontiguousarray(np.stack([np.asarray(iniPVA, dtype=np.float64),
@@ -122,11 +161,12 @@ def qp_solve(order, iniPVA, finPVA, hPolys, times, res=20, max_vel=4.0, max_acc=
 
 
 def qp_solve_vjp(order, iniPVA, finPVA, hPolys, times, grad_z, res=20, max_vel=4.0, max_acc=6.0, m34=1400.0,
-                 settings=None, ctx=None):
+                 settings=None, ctx=None, rows=None):
     """Backward pass through the QP (anet_qp_solve_vjp; the KKT hook of layers.py:129-141 carried through to the
     durations): grad_z (B,N,3,2s) = d loss / d optimal coefficients -> grad_T (B,N) = d loss / d times.  Returns the
-    dict of qp_solve with grad_T added.  Interior-point method only."""
+    dict of qp_solve with grad_T added.  Interior-point method only.  rows: as in qp_solve."""
     ctx = ctx or default_context()
+    settings = _with_rows(settings, rows)
     hp = np.ascontiguousarray(hPolys, dtype=np.float64)
     B, N, M, _ = hp.shape
     state = np.ascontiguousarray(np.stack([np.asarray(iniPVA, dtype=np.float64),
@@ -182,16 +222,17 @@ def _qp_dev_common(order, state, times, hPolys, res, ctx):
 
 
 def qp_solve_dev(order, state, times, hPolys, res=20, max_vel=4.0, max_acc=6.0, m34=1400.0, settings=None, time_grad=False,
-                 stream=None, ctx=None, launch_order=None):
+                 stream=None, ctx=None, launch_order=None, rows=None):
     """anet_qp_solve[_time_grad]_dev: the batched QPSolver::solve with torch CUDA tensors in and out, nothing through the
     host, asynchronous on `stream` (default: torch's current stream).  state (B,2,3,3) = [start PVA, end PVA] (row = axis,
     columns p, v, a), times (B,N), hPolys (B,N,M,4) rows a.x <= b with zero rows as padding.  Returns the dict of
     `qp_solve` as device tensors (grad_T (B,N) with time_grad=True).
     launch_order: optional int32 CUDA tensor (B,), a permutation -- the problem each successive workgroup of the interior-point
     kernel takes (`launch_order_from_counts(previous["iters"])` when re-solving a similar batch: anet_qp_solve_ordered_dev);
-    results do not depend on it."""
+    results do not depend on it.  rows: as in qp_solve."""
     import torch
     ctx = ctx or default_context(times.device.index or 0)
+    settings = _with_rows(settings, rows)
     B, N, M, work, out = _qp_dev_common(order, state, times, hPolys, res, ctx)
     st = stream if stream is not None else torch.cuda.current_stream(times.device).cuda_stream
     sp = ctypes.cast(ctypes.pointer(settings), ctypes.c_void_p) if settings is not None else None
@@ -215,11 +256,12 @@ def qp_solve_dev(order, state, times, hPolys, res=20, max_vel=4.0, max_acc=6.0, 
 
 
 def qp_solve_vjp_dev(order, state, times, hPolys, grad_z, res=20, max_vel=4.0, max_acc=6.0, m34=1400.0, settings=None,
-                     stream=None, ctx=None):
+                     stream=None, ctx=None, rows=None):
     """anet_qp_solve_vjp_dev: solve + backward pass on the device (what a torch.autograd.Function around the layer calls
-    in its backward): grad_z (B,N,3,2s) = d loss / d optimal coefficients -> grad_T (B,N).  Tensors as in `qp_solve_dev`."""
+    in its backward): grad_z (B,N,3,2s) = d loss / d optimal coefficients -> grad_T (B,N).  Tensors and rows as in `qp_solve_dev`."""
     import torch
     ctx = ctx or default_context(times.device.index or 0)
+    settings = _with_rows(settings, rows)
     B, N, M, work, out = _qp_dev_common(order, state, times, hPolys, res, ctx)
     if not (grad_z.is_cuda and grad_z.dtype == torch.float64 and grad_z.is_contiguous() and grad_z.shape == out["coeffs"].shape):
         raise ValueError("grad_z: float64 contiguous CUDA tensor of shape (B,N,3,2s)")
@@ -252,6 +294,16 @@ class QPSolver:
         self.obj_cost_ = -1.0
         self._ctx = ctx
         self._method = QP_METHOD_INTERIOR_POINT
+        self._rows, self._segments = "samples", 1
+
+    def setRowForm(self, form, segments=1):
+        """Extension: "samples" (default: rows at ConstRes samples per piece, the reference's form) or "control_points" (rows on
+        the Bernstein control values of `segments` segments per piece: held for every t; res = segments * 2 * order takes the
+        place of ConstRes; interior point only)."""
+        _row_form_bit(form)
+        if int(segments) < 1:
+            raise ValueError("segments >= 1")
+        self._rows, self._segments = form, int(segments)
 
     def setMethod(self, method):
         """Extension: QP_METHOD_INTERIOR_POINT (default since ABI 2) or QP_METHOD_ADMM (OSQP's algorithm and tolerances)."""
@@ -276,9 +328,10 @@ class QPSolver:
         for i, p in enumerate(hPolys):
             hp[0, i, :p.shape[0]] = p
         t = np.asarray(times, dtype=np.float64)[:seg]
+        res = control_point_res(self.order_, self._segments) if self._rows == "control_points" else self.config.ConstRes
         out = qp_solve(self.order_, np.asarray(iniPVA)[None], np.asarray(finPVA)[None], hp, t[None],
-                       res=self.config.ConstRes, max_vel=self.config.MaxVelBox, max_acc=self.config.MaxAccBox,
-                       settings=qp_settings(method=self._method),
+                       res=res, max_vel=self.config.MaxVelBox, max_acc=self.config.MaxAccBox,
+                       settings=qp_settings(method=self._method, rows=self._rows),
                        ctx=self._ctx)
         result = float(np.float32(out["obj"][0]))          # the reference reads the objective into a float
         if result > 5000 or result < -0.01 or out["status"][0] != 1:

@@ -14,12 +14,12 @@ from .qp import qp_solve_dev, qp_solve_vjp_dev
 
 class _QPSolve(torch.autograd.Function):
     @staticmethod
-    def forward(fctx, times, state, hpolys, order, res, max_vel, max_acc, m34, anet_ctx):
+    def forward(fctx, times, state, hpolys, order, res, max_vel, max_acc, m34, anet_ctx, rows=None):
         t = times.detach().contiguous()
         out = qp_solve_dev(order, state, t, hpolys, res=res, max_vel=max_vel, max_acc=max_acc, m34=m34, time_grad=True,
-                           ctx=anet_ctx)
+                           ctx=anet_ctx, rows=rows)
         fctx.save_for_backward(t, state, hpolys, out["grad_T"], out["status"])
-        fctx.meta = (order, res, max_vel, max_acc, m34, anet_ctx)
+        fctx.meta = (order, res, max_vel, max_acc, m34, anet_ctx, rows)
         fctx.mark_non_differentiable(out["status"])
         # undefined output gradients stay None: a loss that only uses `obj` must not pay the second QP solve of the
         # backward pass through the coefficients
@@ -29,25 +29,26 @@ class _QPSolve(torch.autograd.Function):
     @staticmethod
     def backward(fctx, g_coeffs, g_obj, _g_status):
         t, state, hpolys, env, status = fctx.saved_tensors
-        order, res, max_vel, max_acc, m34, anet_ctx = fctx.meta
+        order, res, max_vel, max_acc, m34, anet_ctx, rows = fctx.meta
         if not fctx.needs_input_grad[0]:
-            return (None,) * 9
+            return (None,) * 10
         grad = torch.zeros_like(t)
         if g_coeffs is not None:
             back = qp_solve_vjp_dev(order, state, t, hpolys, g_coeffs.contiguous(), res=res, max_vel=max_vel,
-                                    max_acc=max_acc, m34=m34, ctx=anet_ctx)
+                                    max_acc=max_acc, m34=m34, ctx=anet_ctx, rows=rows)
             ok = (back["status"] == 1) & (status == 1)
             grad = torch.where(ok[:, None], back["grad_T"], grad)
         if g_obj is not None:
             grad = grad + torch.where((status == 1)[:, None], g_obj[:, None] * env, torch.zeros_like(env))
-        return grad, None, None, None, None, None, None, None, None
+        return grad, None, None, None, None, None, None, None, None, None
 
 
-def qp_layer(times, state, hpolys, order=4, res=20, max_vel=4.0, max_acc=6.0, m34=1400.0, ctx=None):
+def qp_layer(times, state, hpolys, order=4, res=20, max_vel=4.0, max_acc=6.0, m34=1400.0, ctx=None, rows=None):
     """times (B,N) float64 CUDA (may require grad); state (B,2,3,3) = [start PVA, end PVA]; hpolys (B,N,M,4) planner form,
-    zero rows as padding.  Returns (coeffs (B,N,3,2*order), obj (B,), status (B,) int32)."""
+    zero rows as padding.  rows="control_points": the rows on Bernstein control values (res = qp.control_point_res(order,
+    segments)), forward and backward.  Returns (coeffs (B,N,3,2*order), obj (B,), status (B,) int32)."""
     return _QPSolve.apply(times, state.contiguous(), hpolys.contiguous(), int(order), int(res), float(max_vel),
-                          float(max_acc), float(m34), ctx)
+                          float(max_acc), float(m34), ctx, rows)
 
 
 class _MincoSolve(torch.autograd.Function):

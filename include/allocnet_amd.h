@@ -442,6 +442,18 @@ typedef struct anet_qp_settings {
 } anet_qp_settings;
 #define ANET_QP_METHOD_ADMM 0
 #define ANET_QP_METHOD_INTERIOR_POINT 1
+/* Row form, a bit OR-ed into anet_qp_settings.method (anet_qp_solve, _dev, _time_grad, _ordered_dev, _vjp) or into row_order
+ * (anet_qp_assemble[_dev]).  Without it the corridor and box rows are held at `res` samples per piece (the reference's form: nothing
+ * is held between two samples).  With it they are held on Bernstein control values, so for EVERY t of every piece: res must be
+ * k * 2s (k >= 1 Bernstein segments per piece; anything else is ANET_ERR_INVALID), and group j = q*2s + r takes the place of sample
+ * j -- for derivative d = 0, 1, 2 the d-th derivative of the piece restricted to segment q = [q T/k, (q+1) T/k], its Bernstein control
+ * values (degree 2s-1-d) degree-elevated d times to 2s values beta^d_r; the group carries the piece's M corridor rows on beta^0_r and
+ * the 12 box rows +-beta^1_r[ax] <= max_vel, +-beta^2_r[ax] <= max_acc.  Row counts, row order (both ANET_QP_ORDER_*), workspace and
+ * every shape are those of the sample form at the same res; Q, A, b are untouched.  A curve lies in the hull of its control values
+ * and elevated values are convex combinations of them, so a solution satisfies every row for all t up to the primal residual, and
+ * junctions lie in both neighbouring polytopes; the feasible set is smaller than the sample form's, and that of 2k contains that
+ * of k.  Interior point only (with ADMM: ANET_ERR_UNSUPPORTED); assembled in double only (with float_time: ANET_ERR_UNSUPPORTED). */
+#define ANET_QP_ROWS_CONTROL_POINTS 0x100
 void anet_qp_default_settings(anet_qp_settings *s);
 #define ANET_QP_SOLVED 1          /* OSQP_SOLVED                 */
 #define ANET_QP_MAX_ITER_REACHED (-2) /* OSQP_MAX_ITER_REACHED; the reference treats anything but Solved as failure (qp_solver.hpp:346-350) */

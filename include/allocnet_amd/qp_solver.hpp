@@ -39,6 +39,7 @@ class QPSolver {
   double obj_cost_ = -1;
   int last_status_ = 0, last_iters_ = 0;
   int method_ = ANET_QP_METHOD_INTERIOR_POINT;
+  int row_form_ = 0, segments_ = 1;  // setRowForm
   double m34_ = 1400.0;  // the reference's snap-block constant (qp_solver.hpp:212)
   // The time-gradient epilogue (an extension: the reference's caller never asks for it) runs inside solve() only once
   // getTimeGrad() has been asked for; the first request after a plain solve re-solves the remembered problem with it.
@@ -52,11 +53,13 @@ class QPSolver {
     anet::Context &ctx = anet::Context::thread_default();
     anet_qp_settings st;
     anet_qp_default_settings(&st);
-    st.method = method_;
+    st.method = method_ | row_form_;
+    // control-point rows: `segments_` Bernstein segments of 2 * order_ control values per piece take the place of ConstRes
+    const int res = row_form_ ? segments_ * 2 * order_ : config.ConstRes;
     if (with_time_grad)
-      return anet_qp_solve_time_grad(ctx.get(), order_, seg, 1, config.ConstRes, M, config.MaxVelBox, config.MaxAccBox, m34_,
+      return anet_qp_solve_time_grad(ctx.get(), order_, seg, 1, res, M, config.MaxVelBox, config.MaxAccBox, m34_,
                                      state, T, hp, &st, co, obj, status, iters, nullptr, tg);
-    return anet_qp_solve(ctx.get(), order_, seg, 1, config.ConstRes, M, config.MaxVelBox, config.MaxAccBox, m34_, state, T, hp,
+    return anet_qp_solve(ctx.get(), order_, seg, 1, res, M, config.MaxVelBox, config.MaxAccBox, m34_, state, T, hp,
                          &st, co, obj, status, iters, nullptr);
   }
 
@@ -119,6 +122,14 @@ class QPSolver {
   // cost scaling; at OSQP's default max_iter 1-6 % of feasible 8-piece snap problems, by corridor set, still end
   // unsolved -- a failed plan for the caller; profiles/r05_qp_unsolved_admm.txt).
   inline void setMethod(int method) { method_ = method; }
+  // Extension: 0 (default: the corridor and box rows at ConstRes samples per piece, the reference's form -- nothing is held
+  // between two samples) or ANET_QP_ROWS_CONTROL_POINTS (the rows on the Bernstein control values of `segments` segments per
+  // piece: a solution stays in its corridor and inside both boxes for every t; a smaller feasible set, that of 2 * segments
+  // containing that of segments; interior-point method only).
+  inline void setRowForm(int form, int segments = 1) {
+    row_form_ = form;
+    segments_ = segments < 1 ? 1 : segments;
+  }
 
   template <typename MatA, typename MatB, typename Poly, typename Times, typename Sol>
   inline bool solve(const MatA &iniPVA,  // 3*3
