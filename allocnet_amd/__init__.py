@@ -44,6 +44,9 @@ from .avoid import (AvoidOthers, make_avoid_penalty, minco_avoid_partial_grads_d
 from . import obstacle  # noqa: F401
 from .obstacle import (make_obstacle_penalty, minco_obstacle_partial_grads_dev, minco_obstacle_cost_grad_dev,  # noqa: F401
                        minco_obstacle_cost_grad, obstacle_objective_dev)
+from . import body  # noqa: F401
+from .body import (make_body_penalty, box_body, minco_body_partial_grads_dev, minco_body_cost_grad_dev,  # noqa: F401
+                   minco_body_cost_grad, body_objective_dev, traj_body_margin, traj_body_margin_dev)
 from . import time_net  # noqa: F401
 from .time_net import TimeAllocNet  # noqa: F401
 from . import learning_planner  # noqa: F401

@@ -191,6 +191,10 @@ PROTOTYPES = {
     "anet_traj_flat_extrema": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p]),
     "anet_minco_flat_partial_grads_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p,
                                                   c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "anet_minco_body_partial_grads_dev": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int64, c_int64] + [c_void_p] * 3 + [c_int] +
+                                          [c_void_p] * 4),
+    "anet_traj_body_margin_dev": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int64, c_int64] + [c_void_p] * 8),
+    "anet_traj_body_margin": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int64] + [c_void_p] * 7),
     "anet_timenet_create": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "anet_timenet_destroy": (None, [c_void_p]),
     "anet_timenet_device_bytes": (c_int64, [c_void_p]),
@@ -258,6 +262,15 @@ class AvoidPenalty(ctypes.Structure):
 class ObstaclePenalty(ctypes.Structure):
     """struct anet_obstacle_penalty (include/allocnet_amd.h)."""
     _fields_ = [("w", c_double), ("smooth_mu", c_double), ("clearance", c_double), ("res", ctypes.c_int32)]
+
+
+ANET_MAX_BODY_VERTS = 16
+
+
+class BodyPenalty(ctypes.Structure):
+    """struct anet_body_penalty (include/allocnet_amd.h)."""
+    _fields_ = [("w_body", c_double), ("smooth_mu", c_double), ("res", ctypes.c_int32), ("poly_rows", ctypes.c_int32),
+                ("n_verts", ctypes.c_int32), ("pad", ctypes.c_int32), ("verts", (c_double * 3) * ANET_MAX_BODY_VERTS)]
 
 
 ANET_DIST_NONE = 2 ** 31 - 1

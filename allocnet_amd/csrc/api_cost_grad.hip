@@ -50,7 +50,7 @@ int do_propagate(anet_ctx *ctx, int s, const anet::PropArgs &a, hipStream_t st) 
 int basis_table(anet_ctx *ctx, int s, int res, hipStream_t st, const double **out) {
   int rc = ANET_OK;
   *out = nullptr;
-  if (res > 4096) return fail(ctx, ANET_ERR_UNSUPPORTED, "anet_penalty.res too large for the basis table");
+  if (res > kBasisTableMaxRes) return fail(ctx, ANET_ERR_UNSUPPORTED, "anet_penalty.res too large for the basis table");
   for (auto &t : ctx->tabs)
     if (t.s == s && t.res == res) {
       // built on another stream: order this stream behind the build (no host or device-wide synchronisation)

@@ -21,6 +21,7 @@
 //   api_separation.hip exact minimum separation between pairs of trajectories
 //   api_avoid.hip      trajectory-avoidance penalty of the MINCO objective against neighbours of another set of trajectories
 //   api_distance.hip   exact distance field of the voxel map, its query, the obstacle penalty of the MINCO objective
+//   api_body.hip       whole-body corridor terms: body vertices through the flatness attitude, penalty gradients and sampled margin
 //   piece_grad_unit.hip, qp_ipm_fuse_unit.hip: kernels scheduled for ILP, reached through launch functions
 // Only what two or more units use is here.  Nothing here is exported: the library's dynamic symbols stay the anet_* entry
 // points (and the kernels).
@@ -329,7 +330,8 @@ int cost_grad_dev_impl(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batch,
                        double *gradP, double *gradT, double *coeffs_out, void *stream, const double *tau);
 
 // the basis table of k_piece_grad for (order, res) (api_cost_grad.hip owns and builds it; layout: minco_kernels.h, at k_piece_grad):
-// k_flat_piece_grad reads its derivative rows 1..3.  The caller has made the context's device current.
+// k_flat_piece_grad reads its derivative rows 1..3, k_body_piece_grad rows 0..3.  The caller has made the context's device current.
+constexpr int kBasisTableMaxRes = 4096;  // a larger res is refused (ANET_ERR_UNSUPPORTED)
 int basis_table(anet_ctx *ctx, int s, int res, hipStream_t st, const double **out);
 
 #pragma GCC visibility pop

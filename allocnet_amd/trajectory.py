@@ -689,6 +689,22 @@ class Trajectory:
         lo, hi, tilt, bdr = self.getFlatExtrema(flatmap, res)
         return lo > min_thrust and hi < max_thrust and tilt < max_tilt and bdr < max_bdr
 
+    # --- the whole body in the corridor: body vertices through the flatness attitude (body.py) ---------------------
+    def getBodyMargin(self, flatmap, verts, hPolys, res=20, per_piece=False):
+        """Maximum over the pieces of the sampled body margin: a_r . (p(t) + R(q(t)) b_k) - h_r over res + 1 samples of piece i,
+        the rows of hPolys[i] and the body vertices verts (K, 3), q(t) the attitude of the flatness map.  A sampled check.
+        per_piece=True: the arrays (margin, t, row, vert) over the pieces."""
+        from .body import traj_body_margin
+        co, T = self._arrays()
+        if len(hPolys) != len(self.pieces):
+            raise ValueError("one polytope per piece")
+        m, t, r, k = traj_body_margin(flatmap, verts, co, T, _stack_hpolys(hPolys), res, ctx=self._ctx)
+        return (m[0], t[0], r[0], k[0]) if per_piece else float(m.max())
+
+    def checkBodyCorridor(self, flatmap, verts, hPolys, res=20, tol=0.0):
+        """True when every sampled body vertex stays within tol of its piece's polytope; a NaN margin is False."""
+        return bool(self.getBodyMargin(flatmap, verts, hPolys, res) <= tol)
+
     # --- junctions (trajectory.hpp:540-574): direct coefficient reads except at the very end
     def getPositions(self):
         N = self.getPieceNum()

@@ -1030,6 +1030,58 @@ int anet_minco_obstacle_partial_grads_dev(anet_ctx *ctx, const anet_obstacle_pen
                                           const int32_t *sd2, int accumulate, double *gdC, double *gdT,
                                           double *piece_cost /* may be NULL */, void *stream);
 
+/* ---- whole-body corridor terms: body vertices through the flatness attitude ----------------------------------------------
+ * Every other corridor term holds a_r . p(t) <= h_r for the POINT p.  Here the vehicle is a body-fixed convex polytope with vertices
+ * b_k, k < K = n_verts <= ANET_MAX_BODY_VERTS, in the body frame in metres, shared by the batch; its attitude is the one the
+ * trajectory itself implies, q(t) = the quaternion of the flatness map (anet_flat_forward with psi = dpsi = 0, as every
+ * trajectory-level flatness entry point has it) at v(t), a(t), and each vertex  p(t) + R(q(t)) b_k  is held inside the corridor (the
+ * SE(3) constraint of upstream GCOPTER; no counterpart in the reference tree).  A flat vehicle can so roll to pass a slot narrower
+ * than its span.  R(q), q = (w, v), is the homogeneous quadratic form
+ *     R b = (w^2 - v.v) b + 2 (v.b) v + 2 w (v x b),
+ * and for g = a . R(q) b:  dg/dw = 2 w (a.b) + 2 a.(v x b),  dg/dv = -2 (a.b) v + 2 (v.b) a + 2 (a.v) b + 2 w (b x a).  q(t) stays on
+ * the unit sphere and the adjoint of the flatness map applies the exact Jacobian of q, so the radial part of the quaternion's
+ * gradient is annihilated: any extension of R off the sphere gives the same composed gradient.  The penalty is
+ *     J_body = sum_i (T_i/res) sum_(j < res) sum_r sum_k  w_body smoothedL1_mu( a_r . (p(t_j) + R(q(t_j)) b_k) - h_r ),  t_j = j T_i / res,
+ * r over the rows of hpolys[i] in the layout of anet_minco_partial_grads_dev (all-zero rows are padding, M = poly_rows in
+ * [1, ANET_MAX_POLY_ROWS]).  A sample of piece i is tested against polytope i ONLY: next to a junction, where the body already
+ * reaches into the next polytope, this is conservative (the body is held inside the piece's own polytope), as upstream's SE(3)
+ * penalty is.                                                                                                                   */
+#define ANET_MAX_BODY_VERTS 16
+typedef struct anet_body_penalty {
+  double w_body;    /* weight                                                */
+  double smooth_mu; /* smoothedL1 mu in m, > 0                               */
+  int32_t res;      /* samples per piece, >= 1 (and within the basis table)  */
+  int32_t poly_rows; /* M: rows per polytope in `hpolys`, [1, ANET_MAX_POLY_ROWS] */
+  int32_t n_verts;  /* K, [1, ANET_MAX_BODY_VERTS]                           */
+  int32_t pad;
+  double verts[ANET_MAX_BODY_VERTS][3]; /* b_k, finite; entries behind n_verts are not read */
+} anet_body_penalty;
+/* Partial gradients of J_body w.r.t. the coefficients and durations; layouts and the accumulate contract are exactly those of
+ * anet_minco_flat_partial_grads_dev: accumulate = 0: gdC, gdT, piece_cost (may be NULL) are written; != 0: the share is formed
+ * completely and added with one unfused addition, bit for bit the sum of the two separate results.  Lanes in [batch, ld) are never
+ * touched.  Where no term is active (the body far inside its corridor) cost and gradients are exactly 0; a non-finite coefficient,
+ * duration or row field of a piece makes that piece's outputs NaN and no other's.  Orders 3 and 4
+ * (ANET_ERR_UNSUPPORTED otherwise).  ANET_ERR_INVALID: n_verts outside [1, ANET_MAX_BODY_VERTS], res < 1 or above the basis table's
+ * limit (4096), poly_rows outside [1, ANET_MAX_POLY_ROWS], a non-finite vertex,
+ * smooth_mu <= 0, hpolys or another pointer except piece_cost NULL, ld < batch.  batch == 0 returns ANET_OK after the argument checks. */
+int anet_minco_body_partial_grads_dev(anet_ctx *ctx, const anet_flat_params *params, const anet_body_penalty *pen, int s,
+                                      int n_pieces, int64_t batch, int64_t ld, const double *coeffs, const double *T,
+                                      const double *hpolys, int accumulate, double *gdC, double *gdT, double *piece_cost,
+                                      void *stream);
+/* A SAMPLED check, as anet_traj_flat_extrema (the attitude is no polynomial in t: nothing bounds the value between the samples):
+ * per piece the maximum of  a_r . (p(t) + R(q(t)) b_k) - h_r  over t = j T_i / res, j = 0..res (both ends included), the non-padding
+ * rows of hpolys[i] and the vertices; only w_body and smooth_mu of `pen` are not used.  margin [N][ld] (dev) / [batch][N] (host);
+ * t (local time), row, vert (int32): the same shapes, each may be NULL; they are diagnostics, specified by consistency as row and
+ * t of anet_traj_row_margin are: a_row . (p(t) + R(q(t)) b_vert) - h_row reproduces margin.  A piece with no row gives -inf (row,
+ * vert -1, t 0); a non-finite coefficient, duration or row field of that piece gives NaN (the same), for that piece only.
+ * hpolys: [N*M*4][ld] (dev) / [batch][N][M][4] (host).  Orders 2, 3, 4.                                                        */
+int anet_traj_body_margin_dev(anet_ctx *ctx, const anet_flat_params *params, const anet_body_penalty *pen, int s, int n_pieces,
+                              int64_t batch, int64_t ld, const double *coeffs, const double *T, const double *hpolys,
+                              double *margin, double *t, int32_t *row, int32_t *vert, void *stream);
+int anet_traj_body_margin(anet_ctx *ctx, const anet_flat_params *params, const anet_body_penalty *pen, int s, int n_pieces,
+                          int64_t batch, const double *coeffs, const double *T, const double *hpolys, double *margin, double *t,
+                          int32_t *row, int32_t *vert);
+
 /* ---- front-end route on the voxel map: sfc_gen::planPath ----------------------------------------------------------------
  * A collision-free polyline from s to g and its length, by a shortest-path field on the grid, a walk back along it and a
  * line-of-sight shortcut; exact and deterministic (no time budget).  box = {lb[3], hb[3]} (host array), the planner's

@@ -63,6 +63,9 @@ class FlatnessMap {
     }
   }
 
+  // the six parameters as the C ABI takes them (the trajectory-level entry points: getBodyMargin, trajectory_map.hpp)
+  inline const anet_flat_params &params() const { return par; }
+
  private:
   anet_flat_params par = {1.0, 9.8, 0.0, 0.0, 0.0, 1e-4};
   double in[11] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // vel, acc, jer, psi, dpsi of the last forward

@@ -14,11 +14,19 @@
 //     if (checkClearance(traj, voxelMap, 0.3)) ...               // every piece keeps 0.3 m from every surface point
 // d is the smallest distance in metres over the whole trajectory, t its global time, piece its piece and point the index of the
 // nearest point; +inf (t 0, piece -1, point -1) without a finite point, NaN when a piece has a non-finite coefficient.
+//
+// The whole body in the corridor (anet_traj_body_margin; upstream GCOPTER's SE(3) constraint, no counterpart in the reference):
+//     std::vector<anet::Vec3> verts = ...;                        // body vertices in the body frame, at most ANET_MAX_BODY_VERTS
+//     double m = getBodyMargin(traj, flatmap, verts, hPolys, 20);  // max of a_r . (p(t) + R(q(t)) b_k) - h_r, piece i against hPolys[i]
+//     if (checkBodyCorridor(traj, flatmap, verts, hPolys, 20)) ...
+// q(t) is the attitude flatmap.forward gives at the trajectory's v, a, j with psi = 0.  A SAMPLED check: res + 1 samples per piece.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <vector>
 
+#include "flatness.hpp"
 #include "trajectory.hpp"
 #include "voxel_map.hpp"
 
@@ -195,4 +203,47 @@ inline bool checkClearance(const Piece<D> &pc, const PointsOrMap &points, double
   double t;
   int point;
   return getClearance(pc, points, t, point) >= min_dist;
+}
+
+// The sampled body margin: the maximum over the pieces, res + 1 samples of each, the rows of hPolys[i] (one M_i x 4 matrix per piece:
+// rows() and operator()(r, c)) and the body vertices; per_piece (may be null) receives the N margins.  -inf: no row at all.
+template <int D, class HPoly>
+inline double getBodyMargin(const Trajectory<D> &traj, const flatness::FlatnessMap &flatmap, const std::vector<anet::Vec3> &verts,
+                            const std::vector<HPoly> &hPolys, int res = 20, double *per_piece = nullptr) {
+  std::vector<double> co, T;
+  anet::detail::pack_pieces<D>(traj, "getBodyMargin: empty trajectory", co, T);
+  if (hPolys.size() != T.size()) throw anet::Error(ANET_ERR_INVALID, "getBodyMargin: one polytope per piece");
+  if (verts.empty() || verts.size() > (size_t)ANET_MAX_BODY_VERTS)
+    throw anet::Error(ANET_ERR_INVALID, "getBodyMargin: 1 to ANET_MAX_BODY_VERTS body vertices");
+  int M = 1;
+  for (const auto &h : hPolys) M = std::max(M, (int)h.rows());
+  std::vector<double> rows(hPolys.size() * (size_t)M * 4, 0.0);
+  for (size_t i = 0; i < hPolys.size(); ++i)
+    for (int r = 0; r < (int)hPolys[i].rows(); ++r)
+      for (int c = 0; c < 4; ++c) rows[(i * M + r) * 4 + c] = hPolys[i](r, c);
+  anet_body_penalty pen = {};
+  pen.w_body = 0.0;
+  pen.smooth_mu = 1.0;
+  pen.res = res;
+  pen.poly_rows = M;
+  pen.n_verts = (int32_t)verts.size();
+  for (size_t k = 0; k < verts.size(); ++k)
+    for (int c = 0; c < 3; ++c) pen.verts[k][c] = verts[k](c);
+  std::vector<double> m(T.size());
+  anet::Context &ctx = anet::Context::thread_default();
+  ctx.check(anet_traj_body_margin(ctx.get(), &flatmap.params(), &pen, (D + 1) / 2, (int)T.size(), 1, co.data(), T.data(), rows.data(),
+                                  m.data(), nullptr, nullptr, nullptr));
+  double best = m[0];
+  for (size_t i = 0; i < m.size(); ++i) {
+    if (m[i] != m[i]) best = m[i];  // nothing is known about this piece
+    else if (best == best && m[i] > best) best = m[i];
+    if (per_piece) per_piece[i] = m[i];
+  }
+  return best;
+}
+// true when every sampled body vertex stays within tol of its piece's polytope (NaN: false)
+template <int D, class HPoly>
+inline bool checkBodyCorridor(const Trajectory<D> &traj, const flatness::FlatnessMap &flatmap, const std::vector<anet::Vec3> &verts,
+                              const std::vector<HPoly> &hPolys, int res = 20, double tol = 0.0) {
+  return getBodyMargin(traj, flatmap, verts, hPolys, res) <= tol;
 }
