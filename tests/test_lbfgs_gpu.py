@@ -340,6 +340,36 @@ def test_minco_lbfgs_one_launch_agrees_with_lockstep(anet_ctx, s, c, N, M, res):
             assert np.abs(a["wps"] - b["wps"])[same].max() <= tol * 10 * max(1.0, np.abs(b["wps"]).max()), mi
 
 
+@pytest.mark.parametrize("s,c,N,M,res", [(3, 3, 2, 5, 7)])
+def test_minco_lbfgs_one_launch_agrees_with_lockstep_on_failed_searches(anet_ctx, s, c, N, M, res):
+    """The same two execution shapes under a tight search (max_linesearch = 5, min_step = 1e-3, max_step = 1e3), where line
+    searches FAIL: the one-launch kernel's carried copy of the step against the per-launch copy through the error exits, not
+    only 0 / 1 / -1008.  At least three distinct negative return codes occur in the lockstep result (asserted from it alone);
+    at iteration budgets 1 and 4 both shapes return identical (status, iters, evals), and costs equal to the bars above."""
+    import allocnet_amd as aa
+    rng = np.random.default_rng(2)
+    B = 33
+    head, tail, wps, T = random_problem(rng, B, N, c, rest=True)
+    hp = make_corridors(rng, head, tail, wps, M, tight=1.5)
+    pen = aa.make_penalty(rho=20.0, w_corridor=1e3, w_vel=1e2, w_acc=1e2, smooth_mu=1e-2, max_vel=3.0, max_acc=4.0,
+                          res=res, poly_rows=M)
+    both = aa.lbfgs.OPT_WAYPOINTS | aa.lbfgs.OPT_TIMES
+    codes = set()
+    for mi, tol in ((1, 1e-10), (4, 1e-8)):
+        prm = aa.lbfgs_parameter_t(max_linesearch=5, min_step=1e-3, max_step=1e3, max_iterations=mi)
+        a = aa.lbfgs_minco(head, tail, wps, T, s, hpolys=hp, penalty=pen, param=prm, opt=both, ctx=anet_ctx)
+        b = aa.lbfgs_minco(head, tail, wps, T, s, hpolys=hp, penalty=pen, param=prm,
+                           opt=both | aa.lbfgs.OPT_LOCKSTEP, ctx=anet_ctx)
+        codes |= {int(v) for v in b["status"] if v < 0}
+        print("tight search, budget %d: lockstep statuses %s" % (mi, dict(zip(*np.unique(b["status"], return_counts=True)))))
+        assert (a["status"] == b["status"]).all() and (a["iters"] == b["iters"]).all() and (a["evals"] == b["evals"]).all(), \
+            (mi, a["status"], b["status"], a["iters"], b["iters"], a["evals"], b["evals"])
+        assert np.abs(a["cost"] - b["cost"]).max() <= tol * np.abs(b["cost"]).max(), mi
+        assert np.abs(a["T"] - b["T"]).max() <= tol * 10 * max(1.0, np.abs(b["T"]).max()), mi
+        assert np.abs(a["wps"] - b["wps"]).max() <= tol * 10 * max(1.0, np.abs(b["wps"]).max()), mi
+    assert len(codes) >= 3, codes
+
+
 def test_minco_lbfgs_one_launch_vs_lockstep_random_shapes(anet_ctx):
     """Differential fuzz of the two execution shapes over what the fixed cases above leave out: orders 3 / 4, 1..16 pieces,
     every boundary count 2..s (c = 2 with order 4 once hid an in-place overwrite in the scanned sweeps: the pinned rows of
