@@ -28,7 +28,8 @@ from .polytope import (polytope_vertices, polytope_vertices_dev, enumerate_vs, p
 from . import sfc_opt  # noqa: F401
 from .sfc_opt import (sfc_overlap_vertices, sfc_overlap_vertices_dev, sfc_forward_p, sfc_forward_p_dev,  # noqa: F401
                       sfc_backward_grad_p_dev, sfc_backward_p, sfc_backward_p_dev, lbfgs_minco_sfc, lbfgs_minco_sfc_dev,
-                      sfc_default_max_verts, SFC_NO_OVERLAP)
+                      sfc_default_max_verts, SFC_NO_OVERLAP, sfc_shortest_path, sfc_shortest_path_dev, sfc_path_cost_grad_dev, sfc_allot_pieces,
+                      sfc_expand_corridor, sfc_route_waypoints, sfc_first_durations, sfc_setup)
 
 from . import voxel_map  # noqa: F401
 from .voxel_map import VoxelMap, gather_boxes_dev, distance_transform_dev, distance_query_dev, DIST_NONE  # noqa: F401

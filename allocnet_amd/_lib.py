@@ -106,6 +106,13 @@ PROTOTYPES = {
                                  [c_void_p] * 3 + [c_int, c_int, c_double, c_double] + [c_void_p] * 8),
     "anet_lbfgs_minco_sfc": (c_int, [c_void_p, c_int, c_int, c_int, c_int64] + [c_void_p] * 7 +
                              [c_int, c_int, c_double, c_double, c_double, c_int] + [c_void_p] * 9),
+    "anet_sfc_path_cost_grad_dev": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int] + [c_void_p] * 4 + [c_double, c_double] +
+                                    [c_void_p] * 3),
+    "anet_sfc_shortest_path_workspace": (c_int64, [c_int, c_int, c_int64, c_void_p]),
+    "anet_sfc_shortest_path_dev": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int] + [c_void_p] * 6 +
+                                   [c_int, c_double, c_double, c_void_p, c_int] + [c_void_p] * 8),
+    "anet_sfc_shortest_path": (c_int, [c_void_p, c_int, c_int64, c_int] + [c_void_p] * 3 +
+                               [c_double, c_int, c_double, c_double, c_void_p, c_int] + [c_void_p] * 7),
     "anet_firi_default_params": (None, [c_void_p]),
     "anet_firi": (c_int, [c_void_p, c_int64, c_int, c_int, c_int] + [c_void_p] * 10),
     "anet_firi_var": (c_int, [c_void_p, c_int64, c_int, c_int, c_int] + [c_void_p] * 11),

@@ -1,8 +1,9 @@
 // Waypoints as vertex weights of corridor overlaps (sfc_param_kernels.h): overlap enumeration, the transform and its gradient,
-// backward_p, and the corridor-constrained MINCO L-BFGS over (xi, tau) on the lockstep driver of api_lbfgs.hip
-// (include/allocnet_amd.h).
+// backward_p, the corridor-constrained MINCO L-BFGS over (xi, tau) and the shortest route through a corridor
+// (sfc_path_kernels.h), both on the lockstep driver of api_lbfgs.hip (include/allocnet_amd.h).
 #include "api_internal.h"
 #include "sfc_param_kernels.h"
+#include "sfc_path_kernels.h"
 
 #include <cmath>
 
@@ -71,6 +72,31 @@ int opt_eval(void *inst) {
                           e.gT_out, nullptr, e.st, e.tau);
   if (rc) return rc;
   return backward_grad(e.ctx, e.N, e.B, e.ld, e.K, L.x, e.verts, e.W->wps, e.W->norm, e.W->gP, L.g, L.feval, e.st);
+}
+
+// one evaluation of the route length: one launch (sfc_path_kernels.h)
+struct PathEval {
+  anet_ctx *ctx;
+  const anet::LbfgsLayout *L;
+  const double *verts, *start, *goal;
+  int64_t B, ld;
+  int N, K;
+  double eps2, w_norm;
+  hipStream_t st;
+};
+int path_eval(void *inst) {
+  const PathEval &e = *(const PathEval *)inst;
+  hipLaunchKernelGGL(anet::k_sfc_path_eval, sfc_grid(e.B, 1), dim3(anet::kSfcPathBlock), 0, e.st, e.L->x, e.verts, e.start, e.goal, e.B,
+                     e.ld, e.N - 1, e.K, e.eps2, e.w_norm, e.L->feval, e.L->g);
+  ANET_HIP(e.ctx, hipGetLastError());
+  return ANET_OK;
+}
+
+// the parameters of a route solve: the caller's, or the defaults (mem_size 8, past 3, delta 1e-6, g_epsilon 1e-5)
+anet_lbfgs_params path_params(const anet_lbfgs_params *params) {
+  anet_lbfgs_params prm;
+  anet_lbfgs_default_params(&prm);
+  return params ? *params : prm;
 }
 
 }  // namespace
@@ -276,6 +302,129 @@ int anet_lbfgs_minco_sfc(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batc
   if (residual && (rc = sg.download(d_res, N - 1, residual))) return rc;
   if (xi_out && (rc = sg.download(d_xi, nxi, xi_out))) return rc;
   if (coeffs_out && (rc = sg.download(d_co, nco, coeffs_out))) return rc;
+  ANET_HIP(ctx, hipStreamSynchronize(st));
+  return ANET_OK;
+}
+
+int64_t anet_sfc_shortest_path_workspace(int n_pieces, int max_verts, int64_t ld, const anet_lbfgs_params *params) {
+  const anet_lbfgs_params prm = path_params(params);
+  if (prm.mem_size <= 0 || n_pieces < 2 || max_verts < 1 || ld < 1) return -1;
+  return anet::sfc_path_ws(nullptr, n_pieces, max_verts, ld, prm.mem_size, prm.past > 1 ? prm.past : 1).doubles;
+}
+
+int anet_sfc_path_cost_grad_dev(anet_ctx *ctx, int n_pieces, int64_t batch, int64_t ld, int max_verts, const double *start,
+                                const double *goal, const double *xi, const double *verts, double eps, double w_norm, double *cost,
+                                double *grad_xi, void *stream) {
+  ANET_ON_DEVICE(ctx);
+  int rc = check_shape(ctx, "anet_sfc_path_cost_grad_dev", n_pieces, batch, ld, max_verts);
+  if (rc) return rc;
+  if (!(eps >= 0.0) || !(w_norm >= 0.0)) return fail(ctx, ANET_ERR_INVALID, "anet_sfc_path_cost_grad_dev: eps and w_norm must be >= 0");
+  if (batch == 0) return ANET_OK;
+  if (!start || !goal || !xi || !verts || !cost || !grad_xi) return fail(ctx, ANET_ERR_INVALID, "anet_sfc_path_cost_grad_dev: NULL pointer");
+  hipLaunchKernelGGL(anet::k_sfc_path_eval, sfc_grid(batch, 1), dim3(anet::kSfcPathBlock), 0, (hipStream_t)stream, xi, verts, start, goal,
+                     batch, ld, n_pieces - 1, max_verts, eps * eps, w_norm, cost, grad_xi);
+  ANET_HIP(ctx, hipGetLastError());
+  return ANET_OK;
+}
+
+int anet_sfc_shortest_path_dev(anet_ctx *ctx, int n_pieces, int64_t batch, int64_t ld, int max_verts, const double *start,
+                               const double *goal, const double *verts, const int32_t *count, const int32_t *overlap_status,
+                               double *xi, int from_mean, double eps, double w_norm, const anet_lbfgs_params *params, int max_evals,
+                               double *work, double *wps_out, double *length_out, double *cost_out, int32_t *status, int32_t *iters,
+                               int32_t *evals, void *stream) {
+  ANET_ON_DEVICE(ctx);
+  int rc = check_shape(ctx, "anet_sfc_shortest_path_dev", n_pieces, batch, ld, max_verts);
+  if (rc) return rc;
+  if (!(eps >= 0.0) || !(w_norm >= 0.0)) return fail(ctx, ANET_ERR_INVALID, "anet_sfc_shortest_path_dev: eps and w_norm must be >= 0");
+  const int N = n_pieces, K = max_verts, n = (N - 1) * K;
+  const anet_lbfgs_params prm = path_params(params);
+  if (max_evals <= 0) max_evals = ANET_SFC_PATH_MAX_EVALS;
+  if ((rc = check_lbfgs(ctx, n, &prm, max_evals))) return rc;
+  if (batch == 0) return ANET_OK;
+  if (!start || !goal || !verts || !count || !xi || !work || !wps_out)
+    return fail(ctx, ANET_ERR_INVALID, "anet_sfc_shortest_path_dev: NULL pointer");
+  static_assert(anet::kSfcPathBlock == kSfcBlock, "sfc_grid serves both headers");
+  anet::SfcPathWs W = anet::sfc_path_ws(work, N, K, ld, prm.mem_size, prm.past > 1 ? prm.past : 1);
+  anet::LbfgsLayout &L = W.opt;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 blk(kSfcBlock);
+  const int code = (int)ANET_SFC_NO_OVERLAP;
+  // the state rows, the problems that must not run, the start point
+  if ((rc = lbfgs_reset_shared(ctx, L, st))) return rc;
+  hipLaunchKernelGGL(anet::k_sfc_mark_no_overlap, sfc_grid(batch, 1), blk, 0, st, count, overlap_status, batch, ld, N - 1, code, L.is);
+  if (from_mean)
+    hipLaunchKernelGGL(anet::k_sfc_path_mean_start, sfc_grid(batch, N - 1), blk, 0, st, count, L.is, batch, ld, K, code, xi);
+  hipLaunchKernelGGL(anet::k_sfc_path_map, sfc_grid(batch, n), blk, 0, st, L.x, xi, L.is, batch, ld, code, 0);
+  ANET_HIP(ctx, hipGetLastError());
+  PathEval ev{ctx, &L, verts, start, goal, batch, ld, N, K, eps * eps, w_norm, st};
+  rc = lbfgs_drive_shared(ctx, L, batch, prm, max_evals, st, path_eval, &ev, nullptr, 0, false, 0, 0.0, ctx->cancel_flag);
+  if (rc) return rc;
+  // the result (x may have been put back by a failed line search) for the problems that ran
+  hipLaunchKernelGGL(anet::k_sfc_path_map, sfc_grid(batch, n), blk, 0, st, L.x, xi, L.is, batch, ld, code, 1);
+  ANET_HIP(ctx, hipGetLastError());
+  if ((rc = forward_p(ctx, N, batch, ld, K, xi, verts, w_norm, wps_out, W.norm, st))) return rc;
+  if (length_out) {
+    hipLaunchKernelGGL(anet::k_sfc_path_length, sfc_grid(batch, 1), blk, 0, st, start, goal, wps_out, L.is, batch, ld, N - 1, code,
+                       length_out);
+    ANET_HIP(ctx, hipGetLastError());
+  }
+  if ((rc = lbfgs_results_shared(ctx, L, batch, status, iters, evals, cost_out, st))) return rc;
+  if (cost_out) {
+    hipLaunchKernelGGL(anet::k_sfc_no_cost, sfc_grid(batch, 1), blk, 0, st, L.is, batch, ld, code, cost_out);
+    ANET_HIP(ctx, hipGetLastError());
+  }
+  return ANET_OK;
+}
+
+int anet_sfc_shortest_path(anet_ctx *ctx, int n_pieces, int64_t batch, int poly_rows, const double *hpolys, const double *start,
+                           const double *goal, double epsilon, int max_verts, double eps, double w_norm,
+                           const anet_lbfgs_params *params, int max_evals, double *wps_out, double *length_out, int32_t *status,
+                           int32_t *iters, int32_t *evals, int32_t *overlap_status, double *xi_out) {
+  ANET_ON_DEVICE(ctx);
+  int rc = check_shape(ctx, "anet_sfc_shortest_path", n_pieces, batch, batch, max_verts);
+  if (rc) return rc;
+  if (poly_rows < 1) return fail(ctx, ANET_ERR_INVALID, "anet_sfc_shortest_path: poly_rows must be >= 1");
+  if (batch == 0) return ANET_OK;
+  if (!hpolys || !start || !goal || !wps_out) return fail(ctx, ANET_ERR_INVALID, "anet_sfc_shortest_path: NULL pointer");
+  const int N = n_pieces, K = max_verts, M = poly_rows;
+  const int64_t nhp = (int64_t)N * M * 4, nwp = (int64_t)3 * (N - 1), nxi = (int64_t)(N - 1) * K;
+  Stager sg(ctx, batch);
+  const int64_t ld = sg.ld;
+  const int64_t w_opt = anet_sfc_shortest_path_workspace(N, K, ld, params), w_ov = anet_sfc_overlap_workspace(N, batch, M, K);
+  if (w_opt < 0 || w_ov < 0) return fail(ctx, ANET_ERR_INVALID, "anet_sfc_shortest_path: bad lbfgs parameters or shape");
+  double *d_start, *d_goal, *d_hp, *d_xi, *d_verts, *d_wps, *d_len, *d_work;
+  int32_t *count, *ostat;
+  anet::LbfgsResultRows R;
+  rc = sg.stage([&](Stager::Pass &p) {
+    p.in(start, 3, &d_start); p.in(goal, 3, &d_goal); p.in(hpolys, nhp, &d_hp);
+    p.out(nxi, &d_xi); p.rows(3 * nxi, &d_verts);
+    // count | overlap status: one row per waypoint each
+    p.rows(N - 1, &count); p.rows(N - 1, &ostat);
+    // the enumeration and the route solve use the workspace one after the other: one region of the larger
+    p.out(nwp, &d_wps); p.rows(1, &d_len); p.doubles(w_opt > w_ov ? w_opt : w_ov, &d_work);
+    R = anet::lbfgs_result_rows(p.c, ld);
+    // anet_polytope_vertices_dev keeps its (N - 1) batch depths at the head of the staging area (as in anet_lbfgs_minco_sfc)
+    p.at_least(N - 1);
+  });
+  if (rc) return rc;
+  hipStream_t st = ctx->stream;
+  // a problem that does not run keeps its xi: zeros
+  ANET_HIP(ctx, hipMemsetAsync(d_xi, 0, sizeof(double) * (size_t)(nxi * ld), st));
+  if ((rc = anet_sfc_overlap_vertices_dev(ctx, N, batch, ld, M, d_hp, epsilon, K, d_verts, count, ostat, d_work, st))) return rc;
+  rc = anet_sfc_shortest_path_dev(ctx, N, batch, ld, K, d_start, d_goal, d_verts, count, ostat, d_xi, 1, eps, w_norm, params, max_evals,
+                                  d_work, d_wps, d_len, nullptr, R.status, R.iters, R.evals, st);
+  if (rc) return rc;
+  if ((rc = download_results(ctx, batch, R, d_len, status, iters, evals, length_out, st))) return rc;
+  if (overlap_status) {  // [(N-1)][ld] on the device -> [batch][N-1]
+    std::vector<int32_t> h((size_t)(N - 1) * ld);
+    for (int w = 0; w < N - 1; ++w)
+      ANET_HIP(ctx, hipMemcpyAsync(h.data() + (size_t)w * ld, ostat + (int64_t)w * ld, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, st));
+    ANET_HIP(ctx, hipStreamSynchronize(st));
+    for (int64_t b = 0; b < batch; ++b)
+      for (int w = 0; w < N - 1; ++w) overlap_status[b * (N - 1) + w] = h[(size_t)w * ld + b];
+  }
+  if ((rc = sg.download(d_wps, nwp, wps_out))) return rc;
+  if (xi_out && (rc = sg.download(d_xi, nxi, xi_out))) return rc;
   ANET_HIP(ctx, hipStreamSynchronize(st));
   return ANET_OK;
 }

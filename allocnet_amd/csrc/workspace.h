@@ -164,6 +164,18 @@ inline LbfgsLayout sfc_backward_p_ws(double *w, int N, int K, int64_t ld) {
   return lbfgs_layout(w, K, kSfcTinyMem, kSfcTinyPast, (int64_t)(N - 1) * ld);
 }
 
+// The shortest route through a corridor (sfc_path_kernels.h): optimiser state of (N-1) K variables | the three norm rows per
+// waypoint that k_sfc_forward_p writes beside the returned waypoints
+struct SfcPathWs { LbfgsLayout opt; double *norm; int64_t doubles; };
+inline SfcPathWs sfc_path_ws(double *w, int N, int K, int64_t ld, int m, int npf) {
+  Cursor c(w);
+  SfcPathWs L{};
+  L.opt = lbfgs_layout(c, (N - 1) * K, m, npf, ld);
+  L.norm = c.take<double>((int64_t)3 * (N - 1) * ld);
+  L.doubles = c.doubles();
+  return L;
+}
+
 // status | iterations | evaluations of an L-BFGS run (k_lbfgs_results), int32 rows of ld
 struct LbfgsResultRows { int32_t *status, *iters, *evals; int64_t doubles; };
 inline LbfgsResultRows lbfgs_result_rows(Cursor &c, int64_t ld) {

@@ -1226,6 +1226,40 @@ int anet_lbfgs_minco_sfc(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batc
                          double epsilon, int max_verts, double *wps_out, double *cost, double *coeffs_out, int32_t *status,
                          int32_t *iters, int32_t *evals, double *residual, int32_t *overlap_status, double *xi_out);
 
+/* ---- shortest route through a corridor: upstream GCOPTER's getShortestPath in the same variables ---------- */
+/* P_0 = start and P_N = goal are fixed; P_w(xi), w = 1 .. N-1, is the transform above on the vertices of overlap(polytope w-1,
+ * polytope w).  The objective (stated once in allocnet_amd/csrc/sfc_path_kernels.h, one launch per evaluation) is
+ *   L(xi) = sum_{i=0}^{N-1} sqrt(|P_{i+1} - P_i|^2 + eps^2) + w_norm sum_w max(S_w - 1, 0)^3,      eps in metres,
+ * summed per problem in a fixed order (legs ascending, then norm terms ascending).  anet_sfc_shortest_path_dev minimises it by the
+ * lockstep L-BFGS over x = the xi rows, n = (N-1) max_verts.  start, goal [3][ld]; verts, count, overlap_status (may be NULL) are
+ * anet_sfc_overlap_vertices_dev's; xi [(N-1) K][ld] in and out, from_mean != 0: xi is first set to the vertex mean
+ * xi_j = 1 / sqrt(count).  params NULL: anet_lbfgs_default_params (mem_size 8, past 3, delta 1e-6, g_epsilon 1e-5); max_evals <= 0:
+ * ANET_SFC_PATH_MAX_EVALS.  Out: wps_out [3 (N-1)][ld] = anet_sfc_forward_p_dev of the returned xi, length_out [ld] (or NULL) the
+ * UNSMOOTHED length sum_i |P_{i+1} - P_i| of start, wps_out, goal, cost_out [ld] (or NULL) the objective, status / iters / evals
+ * as for anet_lbfgs_minco_sfc_dev.  A problem with a waypoint of count < 2 or overlap status ANET_POLYTOPE_SKIPPED does not run:
+ * status ANET_SFC_NO_OVERLAP, zero counters, length and cost NaN, xi untouched.  The cancel word is honoured.
+ * work: anet_sfc_shortest_path_workspace() doubles -- the optimiser's state (x rows first, then the gradient rows), then the norm
+ * rows of the final anet_sfc_forward_p_dev.                                                                                     */
+#define ANET_SFC_PATH_MAX_EVALS 400
+/* one evaluation alone: cost [ld] = L(xi), grad_xi [(N-1) K][ld] = dL/dxi (one launch of k_sfc_path_eval) */
+int anet_sfc_path_cost_grad_dev(anet_ctx *ctx, int n_pieces, int64_t batch, int64_t ld, int max_verts, const double *start,
+                                const double *goal, const double *xi, const double *verts, double eps, double w_norm, double *cost,
+                                double *grad_xi, void *stream);
+int64_t anet_sfc_shortest_path_workspace(int n_pieces, int max_verts, int64_t ld, const anet_lbfgs_params *params);
+int anet_sfc_shortest_path_dev(anet_ctx *ctx, int n_pieces, int64_t batch, int64_t ld, int max_verts, const double *start,
+                               const double *goal, const double *verts, const int32_t *count, const int32_t *overlap_status,
+                               double *xi, int from_mean, double eps, double w_norm, const anet_lbfgs_params *params, int max_evals,
+                               double *work, double *wps_out, double *length_out, double *cost_out, int32_t *status, int32_t *iters,
+                               int32_t *evals, void *stream);
+/* The host-staged form: hpolys [batch][N][poly_rows][4] (rows a.x <= b, zero rows padding), start, goal [batch][3].  Enumerates
+ * the overlaps (epsilon, max_verts) and runs the route from the vertex mean on one staging buffer.  Out: wps_out [batch][N-1][3],
+ * length_out [batch], status / iters / evals, overlap_status [batch][N-1] and xi_out [batch][(N-1) max_verts] (zeros for a
+ * problem that did not run); each but wps_out may be NULL.                                                                       */
+int anet_sfc_shortest_path(anet_ctx *ctx, int n_pieces, int64_t batch, int poly_rows, const double *hpolys, const double *start,
+                           const double *goal, double epsilon, int max_verts, double eps, double w_norm,
+                           const anet_lbfgs_params *params, int max_evals, double *wps_out, double *length_out, int32_t *status,
+                           int32_t *iters, int32_t *evals, int32_t *overlap_status, double *xi_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,24 @@ inline std::vector<double> planner_form(const Polys &hPolys, int &M) {
     }
   return hp;
 }
+// the next multiple of 8 above the largest overlap count of a corridor in planner form: one enumeration per stacked pair that
+// only counts (room for one vertex reports the true count)
+inline int default_max_verts(anet::Context &ctx, const std::vector<double> &hp, const int N, const int M, const double epsilon) {
+  int most = 0;
+  for (int w = 0; w + 1 < N; ++w) {
+    std::vector<double> rows;
+    for (int q = 0; q < 2; ++q)
+      for (int r = 0; r < M; ++r) {
+        const double *row = &hp[((size_t)(w + q) * M + r) * 4];
+        rows.insert(rows.end(), {row[0], row[1], row[2], -row[3]});
+      }
+    double one[3];
+    int32_t count = 0;
+    ctx.check(anet_polytope_vertices(ctx.get(), 1, 2 * M, rows.data(), epsilon, 1, one, &count, nullptr, nullptr));
+    most = count > most ? count : most;
+  }
+  return (most / 8 + 1) * 8;
+}
 }  // namespace detail
 
 // anet_sfc_overlap_vertices_dev on one corridor (a container of raw-form polytopes with size() and [i]); maxVerts: K
@@ -173,22 +191,7 @@ inline Trajectory<2 * S - 1> optimize(const M1 &headState, const M2 &tailState, 
       for (int a = 0; a < 3; ++a) w0[(size_t)k * 3 + a] = (*inPs)(a, k);
   }
   anet::Context &ctx = anet::Context::thread_default();
-  if (maxVerts <= 0) {  // one enumeration that only counts: room for one vertex reports the true counts
-    int most = 0;
-    for (int w = 0; w + 1 < N; ++w) {
-      std::vector<double> rows;
-      for (int q = 0; q < 2; ++q)
-        for (int r = 0; r < M; ++r) {
-          const double *row = &hp[((size_t)(w + q) * M + r) * 4];
-          rows.insert(rows.end(), {row[0], row[1], row[2], -row[3]});
-        }
-      double one[3];
-      int32_t count = 0;
-      ctx.check(anet_polytope_vertices(ctx.get(), 1, 2 * M, rows.data(), epsilon, 1, one, &count, nullptr, nullptr));
-      most = count > most ? count : most;
-    }
-    maxVerts = (most / 8 + 1) * 8;
-  }
+  if (maxVerts <= 0) maxVerts = detail::default_max_verts(ctx, hp, N, M, epsilon);
   anet_penalty pen = penalty;
   pen.poly_rows = M;
   const anet_lbfgs_params prm = lbfgs::to_c(param);
@@ -214,6 +217,63 @@ inline Trajectory<2 * S - 1> optimize(const M1 &headState, const M2 &tailState, 
     traj.emplace_back(T[i], cm);
   }
   return traj;
+}
+
+// ---- the shortest route through a corridor and the setup on top of it (gcopter.hpp: getShortestPath, setup) ---------------------------
+// what getShortestPath() reports: the polyline ini -> one point in every overlap -> fin
+struct Route {
+  int status = 0, iters = 0, evals = 0;   // lbfgs_optimize's return value (or ANET_SFC_NO_OVERLAP), k, objective evaluations
+  int maxVerts = 0;
+  double length = 0.0;                    // sum of |P_{i+1} - P_i| (unsmoothed)
+  std::vector<double> points;             // [(N+1)][3]: ini, the N - 1 junction points, fin
+  std::vector<int32_t> overlapStatus;     // [(N-1)]
+};
+
+// anet_sfc_shortest_path on one corridor: ini, fin with (i) access, hPolys the N raw-form polytopes; smoothD: the smoothing
+// length of the legs in metres (upstream's smoothD).  maxVerts 0: the next multiple of 8 above the largest overlap count.
+template <class V1, class V2, class Polys>
+inline Route getShortestPath(const V1 &ini, const V2 &fin, const Polys &hPolys, const double smoothD = 1.0e-2, int maxVerts = 0,
+                             const double epsilon = 1.0e-6, const double wNorm = 1.0, const lbfgs::lbfgs_parameter_t *param = nullptr,
+                             const int maxEvals = 0) {
+  const int N = (int)hPolys.size();
+  int M = 1;
+  const std::vector<double> hp = detail::planner_form(hPolys, M);
+  anet::Context &ctx = anet::Context::thread_default();
+  if (maxVerts <= 0) maxVerts = detail::default_max_verts(ctx, hp, N, M, epsilon);
+  Route R;
+  R.maxVerts = maxVerts;
+  R.overlapStatus.assign((size_t)(N - 1), 0);
+  const double a[3] = {ini(0), ini(1), ini(2)}, b[3] = {fin(0), fin(1), fin(2)};
+  std::vector<double> wps((size_t)3 * (N - 1));
+  const anet_lbfgs_params prm = param ? lbfgs::to_c(*param) : anet_lbfgs_params();
+  int32_t status = 0, iters = 0, evals = 0;
+  ctx.check(anet_sfc_shortest_path(ctx.get(), N, 1, M, hp.data(), a, b, epsilon, maxVerts, smoothD, wNorm, param ? &prm : nullptr, maxEvals,
+                                   wps.data(), &R.length, &status, &iters, &evals, R.overlapStatus.data(), nullptr));
+  R.status = status; R.iters = iters; R.evals = evals;
+  R.points.assign(a, a + 3);
+  R.points.insert(R.points.end(), wps.begin(), wps.end());
+  R.points.insert(R.points.end(), b, b + 3);
+  return R;
+}
+
+// pieces per polytope (upstream's lengthPerPiece): ceil(|leg i| / lengthPerPiece), at least 1; points [(N+1)][3] as Route::points
+inline std::vector<int> allotPieces(const std::vector<double> &points, const double lengthPerPiece) {
+  std::vector<int> pieces;
+  for (size_t i = 0; i + 1 < points.size() / 3; ++i) {
+    const double dx = points[3 * i + 3] - points[3 * i], dy = points[3 * i + 4] - points[3 * i + 1], dz = points[3 * i + 5] - points[3 * i + 2];
+    const int k = (int)std::ceil(std::sqrt(dx * dx + dy * dy + dz * dz) / lengthPerPiece);
+    pieces.push_back(k > 1 ? k : 1);
+  }
+  return pieces;
+}
+
+// polytope i repeated pieces[i] times: the corridor optimize() takes when a long polytope carries several pieces
+template <class Polys>
+inline Polys expandCorridor(const Polys &hPolys, const std::vector<int> &pieces) {
+  Polys out;
+  for (size_t i = 0; i < (size_t)hPolys.size(); ++i)
+    for (int k = 0; k < pieces[i]; ++k) out.push_back(hPolys[i]);
+  return out;
 }
 
 }  // namespace sfc_opt
