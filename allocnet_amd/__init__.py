@@ -33,6 +33,9 @@ from .sfc_opt import (sfc_overlap_vertices, sfc_overlap_vertices_dev, sfc_forwar
 
 from . import voxel_map  # noqa: F401
 from .voxel_map import VoxelMap, gather_boxes_dev, distance_transform_dev, distance_query_dev, DIST_NONE  # noqa: F401
+from .voxel_map import voxel_raycast_dev  # noqa: F401
+from . import occupancy  # noqa: F401
+from .occupancy import OccupancyMap, occupancy_params, depth_to_points_dev  # noqa: F401
 from . import path_search  # noqa: F401
 from .path_search import plan_path, plan_paths, PATH_EXACT, PATH_APPROXIMATE, PATH_INVALID_START  # noqa: F401
 from . import flatness  # noqa: F401

@@ -150,6 +150,14 @@ PROTOTYPES = {
     "anet_voxel_path_field_ptr": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "anet_voxel_path_extract_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                             c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "anet_occupancy_workspace": (c_int64, [c_void_p]),
+    "anet_occupancy_reset_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "anet_occupancy_integrate_dev": (c_int, [c_void_p] * 6 + [c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "anet_occupancy_integrate": (c_int, [c_void_p] * 6 + [c_int64, c_int64, c_int, c_void_p]),
+    "anet_occupancy_to_voxels_dev": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int32, c_int, c_void_p, c_void_p]),
+    "anet_depth_to_points_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p,
+                                         c_double, c_double, c_void_p, c_void_p]),
+    "anet_voxel_raycast_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "anet_comm_unique_id": (c_int, [c_void_p, c_void_p]),
     "anet_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "anet_comm_allgather_costs_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
@@ -227,6 +235,15 @@ class FiriParams(ctypes.Structure):
 class VoxelGrid(ctypes.Structure):
     """struct anet_voxel_grid: voxel counts per axis, the map's origin and the voxel edge length."""
     _fields_ = [("size", ctypes.c_int32 * 3), ("origin", c_double * 3), ("scale", c_double)]
+
+
+class OccupancyParams(ctypes.Structure):
+    """struct anet_occupancy_params (include/allocnet_amd.h)."""
+    _fields_ = [("hit", ctypes.c_int32), ("miss", ctypes.c_int32), ("lo", ctypes.c_int32), ("hi", ctypes.c_int32),
+                ("min_range", c_double), ("max_range", c_double)]
+
+
+ANET_OCC_UNKNOWN = -32768
 
 
 class QpDims(ctypes.Structure):

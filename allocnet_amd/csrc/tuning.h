@@ -78,6 +78,9 @@ struct Tuning {
   static constexpr const char *polytope_depth_enumerate = "ANET_POLYTOPE_DEPTH_ENUMERATE";
   // ANET_POLYTOPE_VERTICES_WPP: 1 or 4 waves per polytope in k_polytope_vertices whatever the batch (the results are the same bits)
   static constexpr const char *polytope_vertices_wpp = "ANET_POLYTOPE_VERTICES_WPP";
+  // ANET_OCC_MARKS_ATOMIC: the marks of a scan in one launch of atomicOr on flag bits (k_occ_mark_atomic), not the two launches of
+  // plain byte stores (the grids are the same bits; DESIGN.md 8t has both timings)
+  static constexpr const char *occ_marks_atomic = "ANET_OCC_MARKS_ATOMIC";
 };
 
 // a per-call switch: set (to anything) or not

@@ -213,6 +213,20 @@ class VoxelMap:
         g = g.cpu().numpy()
         return (float(d[0]), g[0]) if single else (d, g)
 
+    def raycast(self, origins, ends):
+        """First hit of the segments origins[i] -> ends[i] ((n, 3) each, or one 3-vector each) on the voxel bytes, by the walk of
+        anet_voxel_raycast_dev: (voxel int32 (n,), t float64 (n,)) numpy -- the linear index of the first visited voxel != 0 and the
+        parameter in [0, 1] it was entered at, HIT_FREE / t = 1 without one, HIT_INVALID / NaN for a row that cannot be walked.
+        Unlike query, the outside of the map is NOT blocked: it is passed through."""
+        import torch
+        single = np.ndim(origins) == 1 if not isinstance(origins, torch.Tensor) else origins.dim() == 1
+        def dev(a):
+            t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+            return t.to(device=self.device, dtype=torch.float64).reshape(-1, 3).contiguous()
+        voxel, t = voxel_raycast_dev(self, self._vox, dev(origins), dev(ends))
+        voxel, t = voxel.cpu().numpy(), t.cpu().numpy()
+        return (int(voxel[0]), float(t[0])) if single else (voxel, t)
+
     def posI2D(self, id):
         """id * scale + oc (a different rounding from the surface's id * stepScale + oc, as in the reference)."""
         return np.asarray(id).astype(np.float64) * self._scale + self._oc
@@ -312,3 +326,27 @@ def distance_query_dev(vm_or_grid, sd2, pos, grad=True, stream=None, ctx=None):
     ctx.check(ctx.lib.anet_voxel_distance_query_dev(ctx.handle, ctypes.byref(grid), _vp(sd2), _vp(pos) if n else None, n,
                                                     _vp(dist) if n else None, _vp(g) if (grad and n) else None, st))
     return dist, g
+
+
+def voxel_raycast_dev(vm_or_grid, voxels, origins, ends, stream=None, ctx=None):
+    """anet_voxel_raycast_dev on tensors: voxels uint8 CUDA (n_voxels,), origins / ends (n, 3) float64 CUDA -> (voxel int32 (n,),
+    t float64 (n,)).  Asynchronous on the current stream."""
+    import torch
+    grid, own = _grid_of(vm_or_grid)
+    ctx = ctx or own or default_context(voxels.device.index or 0)
+    nv = int(grid.size[0]) * int(grid.size[1]) * int(grid.size[2])
+    if voxels.dtype != torch.uint8 or voxels.numel() != nv or not voxels.is_contiguous() or not voxels.is_cuda:
+        raise ValueError("voxel_raycast_dev: voxels must be a contiguous uint8 CUDA tensor with one byte per voxel")
+    for a in (origins, ends):
+        if a.dtype != torch.float64 or a.dim() != 2 or a.shape[1] != 3 or a.device != voxels.device:
+            raise ValueError("voxel_raycast_dev: origins and ends must be (n, 3) float64 tensors on the device of voxels")
+    if origins.shape[0] != ends.shape[0]:
+        raise ValueError("voxel_raycast_dev: as many origins as ends")
+    origins = origins.contiguous(); ends = ends.contiguous()
+    n = origins.shape[0]
+    voxel = torch.empty(n, dtype=torch.int32, device=voxels.device)
+    t = torch.empty(n, dtype=torch.float64, device=voxels.device)
+    st = ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(voxels.device).cuda_stream)
+    ctx.check(ctx.lib.anet_voxel_raycast_dev(ctx.handle, ctypes.byref(grid), _vp(voxels), _vp(origins) if n else None,
+                                             _vp(ends) if n else None, n, _vp(voxel) if n else None, _vp(t) if n else None, st))
+    return voxel, t

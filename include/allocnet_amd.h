@@ -1260,6 +1260,70 @@ int anet_sfc_shortest_path(anet_ctx *ctx, int n_pieces, int64_t batch, int poly_
                            const anet_lbfgs_params *params, int max_evals, double *wps_out, double *length_out, int32_t *status,
                            int32_t *iters, int32_t *evals, int32_t *overlap_status, double *xi_out);
 
+/* ---- occupancy from sensor scans: a log-odds grid by ray carving, depth unprojection, first hit of a segment (no counterpart in the
+ * reference, whose mapCallBack stamps a finished world cloud; csrc/occupancy_kernels.h) ------------------------------------------
+ * The grid: logodds [n_voxels] int16 on the DEVICE in the voxel order of anet_voxel_grid.  ANET_OCC_UNKNOWN marks a voxel no ray
+ * has crossed; every other value is a clamped integer log-odds in units the caller chooses (lo <= L <= hi).
+ * THE WALK of a segment o -> q, shared by the scan and the ray query:
+ *   cell(p)_c = floor((p_c - origin_c) / scale).  This is NOT the truncation of anet_voxel_set_occupied_dev / anet_voxel_query_dev:
+ *   the two agree inside the map, but a point up to one voxel below the origin is OUTSIDE here (cell -1), inside cell 0 there.
+ *   Per axis dir = q_c - o_c, step = sign(dir), bnd = (double)(cur_c + (step > 0)) * scale + origin_c, tmax = (bnd - o_c) / dir,
+ *   tdel = scale / |dir| (both +inf for dir == 0).  While cur != end: tm = the least tmax over the axes with cur_c != end_c; every
+ *   such axis with tmax <= tm + 1e-9 steps, all together, and tmax += tdel; the new cell is visited.  Where crossings tie only the
+ *   diagonal cell is visited, not the other cells of the block (for carving the conservative side).  Visited: the start cell and
+ *   each cell after a step, the last being the end cell.  Cells outside the map are walked through and not touched.  Every
+ *   floating-point operation is rounded on its own (no fused multiply-add), so the cells are reproducible bit for bit.
+ * No input makes a walk longer than 3 * (65536 + 1) steps: the range bounds below, and the refusals of the ray query, see to it. */
+#define ANET_OCC_UNKNOWN (-32768)
+typedef struct anet_occupancy_params {
+  int32_t hit;      /* added to a voxel a return fell in, > 0                                        */
+  int32_t miss;     /* added to a voxel a ray passed through, < 0                                    */
+  int32_t lo, hi;   /* the clamps: -32767 <= lo < 0 < hi <= 32767                                    */
+  double min_range; /* returns closer than this are dropped whole; finite, >= 0                      */
+  double max_range; /* rays are cut here and then only carve; finite, > 0, max_range / scale <= 65536 */
+} anet_occupancy_params;
+/* bytes of the device workspace of a grid: one mark byte per voxel (rounded up), all zero between calls; -1: bad grid */
+int64_t anet_occupancy_workspace(const anet_voxel_grid *grid);
+/* every voxel ANET_OCC_UNKNOWN, every mark 0: call once before the first scan (it is what makes `work` valid) */
+int anet_occupancy_reset_dev(anet_ctx *ctx, const anet_voxel_grid *grid, int16_t *logodds, void *work, void *stream);
+/* One scan from ONE sensor origin (world frame).  records: those of anet_voxel_set_occupied_dev (n of them, `stride` bytes apart,
+ * three float32 (f64 == 0) or float64 (f64 == 1) world coordinates first).  Per record p: a non-finite coordinate skips it;
+ * d = p - o, len = sqrt(dx dx + dy dy + dz dz) summed left to right; len < min_range skips it; len > max_range TRUNCATES the ray to
+ * q = o + d * (max_range / len), else q = p.  The walk o -> q marks every visited cell but the end MISS and the end cell HIT, or
+ * MISS when the ray was truncated.  Then every marked voxel is updated ONCE, however many rays marked it, a hit mark winning
+ * over any number of miss marks:  hit: L = min((L == UNKNOWN ? 0 : L) + hit, hi);  miss only: L = max((L == UNKNOWN ? 0 : L) + miss, lo)
+ * in int32.  The marks are cleared again.  The result is a function of the SET of rays: permuting or duplicating records changes
+ * nothing.  The update runs over the cells within ceil(max_range / scale) + 1 of the sensor's cell, cut to the map, not over the grid.
+ * ANET_ERR_INVALID, with the grid untouched: a bad grid or params, a non-finite origin or one whose cell index reaches 2^30 in
+ * magnitude on an axis, n < 0, a bad stride, a NULL or misaligned pointer.  Asynchronous on `stream`.                           */
+int anet_occupancy_integrate_dev(anet_ctx *ctx, const anet_voxel_grid *grid, const anet_occupancy_params *params, int16_t *logodds,
+                                 const double origin[3], const void *records, int64_t n, int64_t stride, int f64, void *work,
+                                 void *stream);
+/* the same with the records in HOST memory (logodds and work stay on the DEVICE: the map lives there); returns when it is done */
+int anet_occupancy_integrate(anet_ctx *ctx, const anet_voxel_grid *grid, const anet_occupancy_params *params, int16_t *logodds,
+                             const double origin[3], const void *records, int64_t n, int64_t stride, int f64, void *work);
+/* The hand-over to the byte grid: voxels[v] = 1 when L != UNKNOWN and L >= occ, 1 when L == UNKNOWN and unknown_blocked != 0, else 0.
+ * Every byte is written; the bytes are the input of dilate, surface, path, distance and hit.                                    */
+int anet_occupancy_to_voxels_dev(anet_ctx *ctx, const anet_voxel_grid *grid, const int16_t *logodds, int32_t occ, int unknown_blocked,
+                                 uint8_t *voxels, void *stream);
+/* Depth image -> world points.  depth: DEVICE, row-major [height][width], float32 metres (u16 == 0) or uint16 (u16 == 1).  Kept
+ * pixels: (u, v) with u, v in {0, step, 2 step, ...}, row-major, n = ceil(width / step) * ceil(height / step) of them.  K = {fx, fy,
+ * cx, cy}, R [9] row-major and t [3] the camera-to-world pose (HOST).  Per pixel, every operation rounded on its own:
+ *   z = depth * depth_scale;  x = (u - cx) / fx * z;  y = (v - cy) / fy * z;  world_r = (R[r][0] x + R[r][1] y) + R[r][2] z + t[r]
+ * A pixel with z non-finite, z <= min_depth or z > max_depth gives a NaN row, which the integrate call skips.
+ * points: DEVICE double [n][3], ready for anet_occupancy_integrate_dev (stride 24, f64 = 1).                                    */
+int anet_depth_to_points_dev(anet_ctx *ctx, const void *depth, int u16, int width, int height, int step, double depth_scale,
+                             const double K[4], const double R[9], const double t[3], double min_depth, double max_depth,
+                             double *points, void *stream);
+/* First hit along segments on the byte grid: origins, ends [n][3] DEVICE doubles.  voxel[i]: the linear index of the first visited
+ * in-bounds cell with a byte != 0, by the walk above; t[i] (may be NULL): the parameter in [0, 1] at which that cell was entered --
+ * 0 when the start cell is blocked, otherwise the tm of the step that entered it.  No blocked cell met: ANET_HIT_FREE and t = 1.
+ * ANET_HIT_INVALID with t = NaN: a non-finite coordinate, a cell index of 2^30 or more in magnitude, a span of more than 65536
+ * cells on an axis.  Cells OUTSIDE the map are passed through: they are NOT blocked here, unlike in anet_voxel_query_dev, so a
+ * sensor outside the map sees into it and a segment wholly outside is ANET_HIT_FREE.                                            */
+int anet_voxel_raycast_dev(anet_ctx *ctx, const anet_voxel_grid *grid, const uint8_t *voxels, const double *origins, const double *ends,
+                           int64_t n, int32_t *voxel, double *t, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

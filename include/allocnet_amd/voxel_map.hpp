@@ -39,7 +39,11 @@ struct Vec3i {
   }
 };
 
+class OccupancyMap;  // occupancy_map.hpp: writes the voxel bytes from its log-odds (toVoxelMap)
+
 class VoxelMap {
+  friend class OccupancyMap;
+
  public:
   VoxelMap() = default;
   template <class V3i, class V3d>
