@@ -36,6 +36,9 @@ from .voxel_map import VoxelMap, gather_boxes_dev, distance_transform_dev, dista
 from .voxel_map import voxel_raycast_dev  # noqa: F401
 from . import occupancy  # noqa: F401
 from .occupancy import OccupancyMap, occupancy_params, depth_to_points_dev  # noqa: F401
+from . import frontier  # noqa: F401
+from .frontier import occupancy_frontier_dev, label_components_dev, component_stats_dev, view_gain_dev  # noqa: F401
+from .frontier import frustum_points, frontier_clusters, candidate_views, next_view  # noqa: F401
 from . import path_search  # noqa: F401
 from .path_search import plan_path, plan_paths, PATH_EXACT, PATH_APPROXIMATE, PATH_INVALID_START  # noqa: F401
 from . import flatness  # noqa: F401

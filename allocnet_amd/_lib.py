@@ -158,6 +158,14 @@ PROTOTYPES = {
     "anet_depth_to_points_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p,
                                          c_double, c_double, c_void_p, c_void_p]),
     "anet_voxel_raycast_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "anet_occupancy_frontier_dev": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int32] + [c_void_p] * 5),
+    "anet_voxel_components_workspace": (c_int64, [c_void_p]),
+    "anet_voxel_label_components_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "anet_voxel_component_stats_dev": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int32] + [c_void_p] * 7),
+    "anet_occupancy_view_gain_workspace": (c_int64, [c_void_p, c_void_p, ctypes.c_int32]),
+    "anet_occupancy_view_gain_workspace_min": (c_int64, [c_void_p, c_void_p]),
+    "anet_occupancy_view_gain_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int32, c_void_p, c_void_p, ctypes.c_int32,
+                                             c_void_p, ctypes.c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
     "anet_comm_unique_id": (c_int, [c_void_p, c_void_p]),
     "anet_comm_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "anet_comm_allgather_costs_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

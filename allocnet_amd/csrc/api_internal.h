@@ -22,7 +22,8 @@
 //   api_avoid.hip      trajectory-avoidance penalty of the MINCO objective against neighbours of another set of trajectories
 //   api_distance.hip   exact distance field of the voxel map, its query, the obstacle penalty of the MINCO objective
 //   api_body.hip       whole-body corridor terms: body vertices through the flatness attitude, penalty gradients and sampled margin
-//   api_occupancy.hip  log-odds occupancy grid from sensor scans (ray carving), depth unprojection, first hit of a segment on the byte grid
+//   api_occupancy.hip  log-odds occupancy grid from sensor scans (ray carving), depth unprojection, first hit of a segment on the byte grid;
+//                      exploration goals on it (frontier_kernels.h, which builds on occupancy_kernels.h): frontier, components, view gain
 //   piece_grad_unit.hip, qp_ipm_fuse_unit.hip: kernels scheduled for ILP, reached through launch functions
 // Only what two or more units use is here.  Nothing here is exported: the library's dynamic symbols stay the anet_* entry
 // points (and the kernels).

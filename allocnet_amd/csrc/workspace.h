@@ -186,4 +186,32 @@ inline LbfgsResultRows lbfgs_result_rows(Cursor &c, int64_t ld) {
 }
 inline LbfgsResultRows lbfgs_result_rows(double *w, int64_t ld) { Cursor c(w); return lbfgs_result_rows(c, ld); }
 
+// Connected components of a byte grid of n voxels (frontier_kernels.h), labelling and statistics on one buffer: the rank of every
+// root at its own index | the root count of every block of kCompScanBlock voxels, scanned in place | the round of the last merge
+struct VoxCompWs { int32_t *rank, *blocks, *changed; int64_t n_blocks, bytes; };
+inline VoxCompWs voxel_components_ws(void *w, int64_t n) {
+  Cursor c(w);
+  VoxCompWs L{};
+  L.n_blocks = (n + kCompScanBlock - 1) / kCompScanBlock;
+  L.rank = c.take<int32_t>(n);
+  L.blocks = c.take<int32_t>(L.n_blocks);
+  L.changed = c.take<int32_t>(2);
+  L.bytes = c.bytes;
+  return L;
+}
+
+// View gain (frontier_kernels.h): one slot of mark bytes per view of a chunk, each the largest sub-box a view can have -- at most
+// 2 reach + 1 cells per axis, cut to the map -- rounded up to whole kViewSlotAlign bytes; all zero between calls
+struct ViewGainWs { uint8_t *marks; int64_t slot, bytes; };
+inline ViewGainWs view_gain_ws(void *w, const int32_t size[3], int64_t reach, int64_t n_views) {
+  Cursor c(w);
+  ViewGainWs L{};
+  int64_t cells = 1;
+  for (int a = 0; a < 3; ++a) cells *= (2 * reach + 1 < size[a]) ? 2 * reach + 1 : size[a];
+  L.slot = (cells + kViewSlotAlign - 1) / kViewSlotAlign * kViewSlotAlign;
+  L.marks = c.take<uint8_t>(L.slot * n_views);
+  L.bytes = c.bytes;
+  return L;
+}
+
 }  // namespace anet

@@ -14,5 +14,9 @@ constexpr int kFiriEll = 18;         // doubles of ellipsoid state per corridor 
 // Launch order for anet_lbfgs_minco_ordered_dev from the evaluation counts of a previous solve: a counting sort into 4096
 // buckets of 16 evaluations, longest first (the order inside a bucket is whatever the atomics make it: irrelevant here).
 constexpr int kOrderBuckets = 4096;
+// connected components (frontier_kernels.h): voxels per block of the root count / rank pass; view gain: the alignment of a view's
+// slot of mark bytes (the count pass reads and clears it in 16-byte pieces, 256 threads wide)
+constexpr int kCompScanBlock = 256;
+constexpr int kViewSlotAlign = 4096;
 
 }  // namespace anet

@@ -175,3 +175,26 @@ class OccupancyMap:
         if dilate > 0:
             vm.dilate(dilate)
         return vm
+
+    # ---- exploration goals (frontier.py) -----------------------------------------------------------
+    def frontier(self, occ=0, box=None, out=None):
+        """(mask uint8 CUDA (n_voxels,), count): the known voxels below `occ` with an unknown face neighbour inside the map, in
+        the cell box (lo, ext) when one is given."""
+        from .frontier import occupancy_frontier_dev
+        return occupancy_frontier_dev(self, self._logodds, occ, box, out)
+
+    def frontierClusters(self, occ=0, min_size=8, connectivity=26, box=None):
+        """The frontier grouped into connected clusters of at least min_size voxels (frontier.frontier_clusters)."""
+        from .frontier import frontier_clusters
+        return frontier_clusters(self, occ, min_size, connectivity, box)
+
+    def viewGain(self, view_R, view_t, pts, occ=0, work=None):
+        """Per pose (R (V, 3, 3), t (V, 3); arrays or CUDA tensors) the number of distinct unknown voxels a scan with the
+        sensor-frame template pts (R, 3) would cross, by this map's params: (V,) int32 numpy.  -1: a non-finite pose."""
+        import torch
+        from .frontier import view_gain_dev
+        def dev(a, shape):
+            t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+            return t.to(device=self.device, dtype=torch.float64).reshape(shape).contiguous()
+        return view_gain_dev(self, self.params, self._logodds, dev(view_R, (-1, 9)), dev(view_t, (-1, 3)), dev(pts, (-1, 3)), occ,
+                             work=work).cpu().numpy()

@@ -242,6 +242,14 @@ class VoxelMap:
         from .path_search import path_field_dev
         return path_field_dev(self, starts, lb, hb)
 
+    # ---- connectivity of the free space -------------------------------------------------------------
+    def components(self, connectivity=26, free=True):
+        """Connected components of the free voxels (free=False: of the blocked ones): int32 CUDA labels (n_voxels,), -1 off the
+        set, else the least voxel index of the component -- two voxels are mutually reachable exactly when their labels agree."""
+        from .frontier import label_components_dev
+        mask = (self._vox == 0) if free else (self._vox != 0)
+        return label_components_dev(self, mask.to(self._vox.dtype), connectivity)
+
     # ---- convexCover's per-segment selection --------------------------------------------------------
     def gather_boxes(self, bd, points=None):
         """For each box k of bd (K, 6, 4) (rows h . [p; 1] < 0 inside), the surface points inside it, in surface order,

@@ -1324,6 +1324,56 @@ int anet_depth_to_points_dev(anet_ctx *ctx, const void *depth, int u16, int widt
 int anet_voxel_raycast_dev(anet_ctx *ctx, const anet_voxel_grid *grid, const uint8_t *voxels, const double *origins, const double *ends,
                            int64_t n, int32_t *voxel, double *t, void *stream);
 
+/* ---- exploration goals on the occupancy grid: frontier, connected components, view gain (csrc/frontier_kernels.h) ----------------
+ * Everything below is integer, or the walk above: each result is a function of its inputs alone, bit for bit.
+ * The frontier: mask[v] = 1 when logodds[v] != ANET_OCC_UNKNOWN, logodds[v] < occ (the threshold of anet_occupancy_to_voxels_dev, so
+ * "free" means the same in both), v lies in the box of cells [box_lo, box_lo + box_ext) (both NULL: the whole map) and at least one
+ * of the six face neighbours INSIDE the map is ANET_OCC_UNKNOWN; a neighbour outside the map is not unknown space.  Every byte of
+ * mask [n_voxels] is written, 0 outside the box.  count_dev (DEVICE, may be NULL): the number of ones.  ANET_ERR_INVALID before
+ * anything is written: a bad grid, a NULL pointer, one of box_lo / box_ext NULL, a box not inside the map (lo >= 0, ext >= 1,
+ * lo + ext <= size).  Asynchronous on `stream`.                                                                                 */
+int anet_occupancy_frontier_dev(anet_ctx *ctx, const anet_voxel_grid *grid, const int16_t *logodds, int32_t occ, const int32_t box_lo[3],
+                                const int32_t box_ext[3], uint8_t *mask, int64_t *count_dev, void *stream);
+/* Connected components of a byte grid (any: a frontier mask, or the free bytes of a voxel map -- two voxels are mutually reachable
+ * exactly when their labels are equal).  mask [n_voxels] DEVICE, a voxel is in the set when its byte != 0; connectivity 6 (faces) or
+ * 26 (faces, edges, corners).  labels [n_voxels] int32 DEVICE: -1 where mask[v] == 0, otherwise the SMALLEST linear voxel index of
+ * v's component -- a function of the mask alone.  Label equivalence with root chasing: tiles of 8 x 8 x 4 voxels are resolved in
+ * LDS, the links across tile borders by atomic minima on root labels, then every label is set to its root; rounds of the last two
+ * steps repeat until one links nothing (the word that says so is read once per two rounds; the loop is bounded by the voxel count).
+ * rounds_host (HOST, may be NULL): the rounds that ran (a multiple of two: they are issued in pairs).  work: anet_voxel_components_workspace()
+ * bytes, 8-byte aligned (-1: bad grid), shared with anet_voxel_component_stats_dev.  Returns when the labels are final.          */
+int64_t anet_voxel_components_workspace(const anet_voxel_grid *grid);
+int anet_voxel_label_components_dev(anet_ctx *ctx, const anet_voxel_grid *grid, const uint8_t *mask, int connectivity, int32_t *labels,
+                                    void *work, int32_t *rounds_host, void *stream);
+/* The table of the components of `labels` (the output above), in ASCENDING order of root label (the roots are the voxels with
+ * labels[v] == v): n_components_dev [1] the true number, even above max_components; for the first max_components of them root
+ * [max], count [max] the voxels, sum_xyz [max][3] int64 the sums of the integer cell coordinates, bbox [max][6] the inclusive cell
+ * box (lo x y z, hi x y z).  Voxels of later components are ignored.  All DEVICE; max_components == 0 counts only (the four
+ * tables may then be NULL).  work: as above; a root's rank is left at its own index in it.  Asynchronous on `stream`.            */
+int anet_voxel_component_stats_dev(anet_ctx *ctx, const anet_voxel_grid *grid, const int32_t *labels, int32_t max_components,
+                                   int32_t *n_components_dev, int32_t *root, int32_t *count, int64_t *sum_xyz, int32_t *bbox, void *work,
+                                   void *stream);
+/* View gain: gain[v] = the number of DISTINCT voxels in U_v, the unknown voxels a scan with the template `pts` from pose v would
+ * cross.  Per template point p_s = pts[r] (sensor frame): the world point p_c = (R[c][0] x + R[c][1] y) + R[c][2] z + t[c], each
+ * operation rounded on its own (anet_depth_to_points_dev's expression); the ray from o = t exactly as a scan forms it (a non-finite
+ * point or one closer than min_range is skipped, one beyond max_range is cut to o + d * (max_range / len)); the walk above at the
+ * scan's span limit.  Per visited cell: outside the map: continue; L != UNKNOWN and L >= occ: stop (an occupied cell blocks and is
+ * not counted); L == UNKNOWN: the cell is in U_v; known free: continue.  The end cell is treated like any other.
+ * A view with a non-finite entry in R or t gets -1, the other views are unaffected; a view in an occupied cell gets 0 by the rule.
+ * gain is a function of the SET of template points, and on a map without an occupied voxel it equals the number of voxels
+ * anet_occupancy_integrate_dev turns from UNKNOWN to known when given the same world points from the same origin.
+ * view_R [V][9] row-major, view_t [V][3], pts [n_pts][3], gain [V]: all DEVICE.  work: one mark byte per cell of a view's sub-box
+ * (the cells within ceil(max_range / scale) + 1 of the view's cell, cut to the map), a slot per view, all zero between calls like
+ * the marks of anet_occupancy_workspace (a fresh buffer is zeroed by the caller once).  Views run in chunks of as many slots as
+ * work_bytes holds -- one mark launch and one count-and-clear launch per chunk -- and the result does not depend on the chunking.
+ * anet_occupancy_view_gain_workspace: the bytes for n_views in one chunk; _min: for one view; -1: bad grid or params.
+ * ANET_ERR_INVALID: a bad grid or params, negative counts, a NULL pointer, work not 16-byte aligned, work_bytes below _min.      */
+int64_t anet_occupancy_view_gain_workspace(const anet_voxel_grid *grid, const anet_occupancy_params *params, int32_t n_views);
+int64_t anet_occupancy_view_gain_workspace_min(const anet_voxel_grid *grid, const anet_occupancy_params *params);
+int anet_occupancy_view_gain_dev(anet_ctx *ctx, const anet_voxel_grid *grid, const anet_occupancy_params *params, const int16_t *logodds,
+                                 int32_t occ, const double *view_R, const double *view_t, int32_t n_views, const double *pts,
+                                 int32_t n_pts, int32_t *gain, void *work, int64_t work_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,9 +4,12 @@
 // (the voxels no ray crossed) and what has changed (a voxel seen through often enough becomes free again); the rules are in
 // allocnet_amd.h.  Constructed like VoxelMap, plus the parameters; toVoxelMap writes the bytes dilate, getSurf, planPath and the
 // trajectory checks take.  voxel_map::raycast is the first hit of a segment on a VoxelMap's bytes (a line-of-sight test, or the
-// sensor of a simulation).
+// sensor of a simulation).  frontier / frontierClusters / viewGain say where to look next on a map with unknown space, and
+// voxel_map::components labels the mutually reachable free voxels of a VoxelMap (anet_occupancy_frontier_dev,
+// anet_voxel_label_components_dev, anet_voxel_component_stats_dev, anet_occupancy_view_gain_dev).
 // Vectors are duck-typed as in core.hpp: anything with (i) access goes in.  C++14, no Eigen or HIP headers.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -31,6 +34,55 @@ inline anet_occupancy_params occupancyParams(double p_hit = 0.7, double p_miss =
   p.max_range = max_range;
   return p;
 }
+
+// a frontier cluster: its least voxel index, voxel count, world centroid origin + (sum / count + 0.5) scale, inclusive cell box
+struct FrontierCluster {
+  int32_t root, count;
+  double centroid[3];
+  int32_t lo[3], hi[3];
+};
+
+namespace detail {
+// device bytes for the length of a call
+struct DevBytes {
+  anet::Context &ctx;
+  double *p = nullptr;
+  size_t doubles;
+  DevBytes(anet::Context &c, size_t bytes) : ctx(c), doubles((bytes + 7) / 8 + 1) { ctx.check(anet_dev_alloc(ctx.get(), doubles, &p)); }
+  DevBytes(const DevBytes &) = delete;
+  DevBytes &operator=(const DevBytes &) = delete;
+  ~DevBytes() { anet_dev_free(p); }
+  template <class T>
+  void put(const T *host, size_t n) {
+    std::vector<double> buf((n * sizeof(T) + 7) / 8);
+    std::memcpy(buf.data(), host, n * sizeof(T));
+    ctx.check(anet_dev_upload(ctx.get(), p, buf.data(), buf.size()));
+  }
+  template <class T>
+  std::vector<T> get(size_t n) const {
+    std::vector<double> buf((n * sizeof(T) + 7) / 8);
+    ctx.check(anet_dev_download(ctx.get(), buf.data(), p, buf.size()));
+    std::vector<T> out(n);
+    std::memcpy(out.data(), buf.data(), n * sizeof(T));
+    return out;
+  }
+};
+
+// labels of the bytes != 0 of `mask` (host, one per voxel): -1 off the set, else the least voxel index of the component; the
+// device labels and the workspace stay in labels_out / work_out when given
+inline std::vector<int32_t> label(anet::Context &ctx, const anet_voxel_grid &g, const std::vector<uint8_t> &mask, int connectivity,
+                                  DevBytes *labels_out = nullptr, DevBytes *work_out = nullptr) {
+  const size_t n = mask.size();
+  const int64_t ws = anet_voxel_components_workspace(&g);
+  if (ws < 0) throw anet::Error(ANET_ERR_INVALID, "voxel_map::components: bad grid");
+  DevBytes dm(ctx, n), own_l(ctx, labels_out ? 8 : n * 4), own_w(ctx, work_out ? 8 : (size_t)ws);
+  DevBytes &dl = labels_out ? *labels_out : own_l, &dw = work_out ? *work_out : own_w;
+  dm.put(mask.data(), n);
+  ctx.check(anet_voxel_label_components_dev(ctx.get(), &g, (const uint8_t *)dm.p, connectivity, (int32_t *)dl.p, dw.p, nullptr,
+                                            anet_stream(ctx.get())));
+  return dl.get<int32_t>(n);
+}
+}  // namespace detail
 
 class OccupancyMap {
  public:
@@ -141,6 +193,75 @@ class OccupancyMap {
     vm.dist_valid_[0] = vm.dist_valid_[1] = false;
   }
 
+  // overwrite the grid with a host copy (a saved map): one value per voxel
+  void setLogOdds(const std::vector<int16_t> &L) {
+    if ((int64_t)L.size() != voxNum_) throw anet::Error(ANET_ERR_INVALID, "voxel_map::OccupancyMap::setLogOdds: one value per voxel");
+    std::vector<double> buf((size_t)((voxNum_ * 2 + 7) / 8));
+    std::memcpy(buf.data(), L.data(), (size_t)voxNum_ * 2);
+    anet::Context &ctx = anet::Context::thread_default();
+    ctx.check(anet_dev_upload(ctx.get(), (double *)logodds_, buf.data(), buf.size()));
+  }
+
+  // the frontier: one byte per voxel, 1 where the voxel is known, below occ and has an unknown face neighbour inside the map
+  std::vector<uint8_t> frontier(int occ = 0, int64_t *count = nullptr) const {
+    anet::Context &ctx = anet::Context::thread_default();
+    detail::DevBytes dm(ctx, (size_t)voxNum_), dc(ctx, 8);
+    ctx.check(anet_occupancy_frontier_dev(ctx.get(), &g_, (const int16_t *)logodds_, occ, nullptr, nullptr, (uint8_t *)dm.p, (int64_t *)dc.p,
+                                          anet_stream(ctx.get())));
+    if (count) *count = dc.get<int64_t>(1)[0];
+    return dm.get<uint8_t>((size_t)voxNum_);
+  }
+
+  // the frontier grouped into connected clusters (6 or 26 neighbours) of at least min_size voxels, in ascending root order
+  std::vector<FrontierCluster> frontierClusters(int occ = 0, int min_size = 8, int connectivity = 26, int max_components = 65536) const {
+    anet::Context &ctx = anet::Context::thread_default();
+    const size_t n = (size_t)voxNum_, m = (size_t)max_components;
+    const int64_t ws = anet_voxel_components_workspace(&g_);
+    detail::DevBytes dl(ctx, n * 4), dw(ctx, (size_t)ws), dn(ctx, 8), dr(ctx, m * 4), dc(ctx, m * 4), ds(ctx, m * 24), db(ctx, m * 24);
+    detail::label(ctx, g_, frontier(occ), connectivity, &dl, &dw);
+    ctx.check(anet_voxel_component_stats_dev(ctx.get(), &g_, (const int32_t *)dl.p, max_components, (int32_t *)dn.p, (int32_t *)dr.p,
+                                             (int32_t *)dc.p, (int64_t *)ds.p, (int32_t *)db.p, dw.p, anet_stream(ctx.get())));
+    const size_t k = std::min<size_t>((size_t)dn.get<int32_t>(1)[0], m);
+    const std::vector<int32_t> root = dr.get<int32_t>(k), cnt = dc.get<int32_t>(k), box = db.get<int32_t>(k * 6);
+    const std::vector<int64_t> sum = ds.get<int64_t>(k * 3);
+    std::vector<FrontierCluster> out;
+    for (size_t i = 0; i < k; ++i) {
+      if (cnt[i] < min_size) continue;
+      FrontierCluster c;
+      c.root = root[i];
+      c.count = cnt[i];
+      for (int a = 0; a < 3; ++a) {
+        c.centroid[a] = g_.origin[a] + ((double)sum[i * 3 + a] / (double)cnt[i] + 0.5) * g_.scale;
+        c.lo[a] = box[i * 6 + a];
+        c.hi[a] = box[i * 6 + 3 + a];
+      }
+      out.push_back(c);
+    }
+    return out;
+  }
+
+  // per pose (R [V][9] row-major camera-to-world, t [V][3]) the number of distinct unknown voxels a scan with the sensor-frame
+  // template pts [n][3] would cross, by this map's parameters; -1 for a pose with a non-finite entry
+  std::vector<int32_t> viewGain(const std::vector<double> &R, const std::vector<double> &t, const std::vector<double> &pts, int occ = 0) const {
+    const size_t V = t.size() / 3, n = pts.size() / 3;
+    if (R.size() != V * 9 || t.size() != V * 3 || pts.size() != n * 3)
+      throw anet::Error(ANET_ERR_INVALID, "voxel_map::OccupancyMap::viewGain: R [V][9], t [V][3], pts [n][3]");
+    if (V == 0) return std::vector<int32_t>();
+    anet::Context &ctx = anet::Context::thread_default();
+    // at most eight views per chunk: a slot of marks is megabytes on a large map at a long range
+    const int64_t ws = anet_occupancy_view_gain_workspace(&g_, &prm_, (int32_t)std::min<size_t>(V, 8));
+    if (ws < 0) throw anet::Error(ANET_ERR_INVALID, "voxel_map::OccupancyMap::viewGain: bad parameters");
+    detail::DevBytes dR(ctx, V * 72), dt(ctx, V * 24), dp(ctx, n * 24), dg(ctx, V * 4), dw(ctx, (size_t)ws);
+    dR.put(R.data(), R.size());
+    dt.put(t.data(), t.size());
+    if (n) dp.put(pts.data(), pts.size());
+    const std::vector<double> zero(dw.doubles, 0.0);  // the marks start at zero (and are zero again afterwards)
+    ctx.check(anet_dev_upload(ctx.get(), dw.p, zero.data(), zero.size()));
+    ctx.check(anet_occupancy_view_gain_dev(ctx.get(), &g_, &prm_, (const int16_t *)logodds_, occ, dR.p, dt.p, (int32_t)V, dp.p, (int32_t)n,
+                                           (int32_t *)dg.p, dw.p, ws, anet_stream(ctx.get())));
+    return dg.get<int32_t>(V);
+  }
+
   // host copy of the grid: ANET_OCC_UNKNOWN where nothing was observed
   std::vector<int16_t> getLogOdds() const {
     std::vector<double> buf((size_t)((voxNum_ * 2 + 7) / 8));
@@ -187,6 +308,14 @@ inline int32_t raycast(const VoxelMap &map, const A &o, const B &q, double &t) {
   int32_t v;
   std::memcpy(&v, &h[7], sizeof(v));
   return v;
+}
+
+// Connected components of the FREE voxels of a map (6 or 26 neighbours): one label per voxel, -1 for a blocked voxel, else the
+// least voxel index of the component -- two free voxels are mutually reachable exactly when their labels are equal.
+inline std::vector<int32_t> components(const VoxelMap &map, int connectivity = 26) {
+  std::vector<uint8_t> free_bytes = map.getVoxels();
+  for (uint8_t &b : free_bytes) b = b == 0 ? 1 : 0;
+  return detail::label(anet::Context::thread_default(), map.grid(), free_bytes, connectivity);
 }
 
 }  // namespace voxel_map
