@@ -51,6 +51,9 @@ from .avoid import (AvoidOthers, make_avoid_penalty, minco_avoid_partial_grads_d
 from . import obstacle  # noqa: F401
 from .obstacle import (make_obstacle_penalty, minco_obstacle_partial_grads_dev, minco_obstacle_cost_grad_dev,  # noqa: F401
                        minco_obstacle_cost_grad, obstacle_objective_dev)
+from . import stop  # noqa: F401
+from .stop import (make_stop_penalty, minco_stop_partial_grads_dev, minco_stop_cost_grad_dev, minco_stop_cost_grad,  # noqa: F401
+                   stop_objective_dev, traj_stop_margin, traj_stop_margin_dev, traj_stop_check)
 from . import body  # noqa: F401
 from .body import (make_body_penalty, box_body, minco_body_partial_grads_dev, minco_body_cost_grad_dev,  # noqa: F401
                    minco_body_cost_grad, body_objective_dev, traj_body_margin, traj_body_margin_dev)

@@ -144,6 +144,10 @@ PROTOTYPES = {
     "anet_voxel_distance_query_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "anet_minco_obstacle_partial_grads_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                                       c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "anet_minco_stop_partial_grads_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "anet_traj_stop_margin_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64] + [c_void_p] * 9),
+    "anet_traj_stop_margin": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64] + [c_void_p] * 8),
     "anet_voxel_path_workspace": (c_int64, [c_void_p, c_int64]),
     "anet_voxel_path_field_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                           c_void_p]),
@@ -294,6 +298,12 @@ class AvoidPenalty(ctypes.Structure):
 class ObstaclePenalty(ctypes.Structure):
     """struct anet_obstacle_penalty (include/allocnet_amd.h)."""
     _fields_ = [("w", c_double), ("smooth_mu", c_double), ("clearance", c_double), ("res", ctypes.c_int32)]
+
+
+class StopPenalty(ctypes.Structure):
+    """struct anet_stop_penalty (include/allocnet_amd.h)."""
+    _fields_ = [("w", c_double), ("smooth_mu", c_double), ("clearance", c_double), ("a_brake", c_double), ("t_react", c_double),
+                ("speed_eps", c_double), ("res", ctypes.c_int32)]
 
 
 ANET_MAX_BODY_VERTS = 16

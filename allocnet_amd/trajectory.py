@@ -705,6 +705,27 @@ class Trajectory:
         """True when every sampled body vertex stays within tol of its piece's polytope; a NaN margin is False."""
         return bool(self.getBodyMargin(flatmap, verts, hPolys, res) <= tol)
 
+    # --- stop within known space: speed against the distance field of the map (stop.py) ------------------------------
+    def getStopMargin(self, vm, a_brake, t_react=0.0, clearance=0.0, res=20, per_piece=False):
+        """(margin, t, piece): the least d(p) - clearance - t_react |v| - v.v / (2 a_brake) over res + 1 samples of every piece,
+        d the distance field of the VoxelMap vm (walls count; on a map made with unknown="blocked" the distance to everything not
+        seen to be free), the global time at which it is attained and its piece.  A sampled check.  per_piece=True: the arrays
+        (margin, t, speed, dist) over the pieces, t in local time."""
+        from .stop import traj_stop_margin
+        co, T = self._arrays()
+        m, t, sp, d = traj_stop_margin(co, T, vm, a_brake, t_react, clearance, res, ctx=self._ctx)
+        if per_piece:
+            return m[0], t[0], sp[0], d[0]
+        if np.isnan(m[0]).any():
+            i = int(np.isnan(m[0]).argmax())
+            return float("nan"), float(T[0, :i].sum()), i
+        i = int(m[0].argmin())
+        return float(m[0, i]), float(T[0, :i].sum() + t[0, i]), i
+
+    def checkStoppable(self, vm, a_brake, t_react=0.0, clearance=0.0, res=20):
+        """True when the sampled stop margin is >= 0 on every piece; a NaN margin is False."""
+        return bool(self.getStopMargin(vm, a_brake, t_react, clearance, res)[0] >= 0.0)
+
     # --- junctions (trajectory.hpp:540-574): direct coefficient reads except at the very end
     def getPositions(self):
         N = self.getPieceNum()

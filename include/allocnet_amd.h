@@ -1030,6 +1030,66 @@ int anet_minco_obstacle_partial_grads_dev(anet_ctx *ctx, const anet_obstacle_pen
                                           const int32_t *sd2, int accumulate, double *gdC, double *gdT,
                                           double *piece_cost /* may be NULL */, void *stream);
 
+/* ---- stop within known space: speed coupled with the distance field, penalty and sampled check (no counterpart in the reference) ----
+ * With the field of a map whose blocked set is occupied OR unknown (OccupancyMap::toVoxelMap(unknown = blocked)), d is the distance
+ * to everything the vehicle has not seen to be free.  A vehicle that reacts for t_react and then brakes at a_brake comes to rest within
+ * t_react |v| + v.v / (2 a_brake) of where it is; this term holds that ball, grown by `clearance`, inside free space, which none of
+ * the corridor, obstacle and collision terms does: they bound where the vehicle is, not how fast it moves towards what it cannot see.
+ * Sampling, layouts, orders, the sum and the accumulate contract are those of anet_minco_obstacle_partial_grads_dev: sample j < res
+ * of piece i at sigma = (double)j / (double)res, tau = sigma * T_i, one rounding each; p, v, a the position, velocity and acceleration
+ * of the piece at tau; d and grad d from anet_voxel_distance_query_dev's rule at p (the same cell rule, clamping and sentinels).
+ *     s_eps = sqrt(v.v + eps^2)                            (eps = speed_eps)
+ *     g     = t_react s_eps + (v.v) hb + clearance - d     (hb = 0.5 / a_brake, one IEEE division on the host)
+ *     Phi   = w smoothedL1_mu(g)         phi' = smoothedL1_mu'(g)
+ *     kappa = t_react / s_eps + 1 / a_brake
+ *     F     = -w phi' grad d             G = w phi' kappa v
+ *     J_stop(b)        = sum_i (T_i / res) sum_(j < res) Phi
+ *     dJ/dc[i][ax][k]  = (T_i/res) sum_j ( F_ax tau^k + G_ax k tau^(k-1) )        (k: the power of tau this coefficient multiplies)
+ *     dJ/dT_i          = (1/res) sum_j Phi + (T_i/res) sum_j sigma (F . v + G . a)
+ * With t_react == 0 the terms in s_eps are absent from g and kappa (speed_eps may then be 0, and a sample at rest is no singular
+ * point).  Three properties:
+ *   - s_eps >= |v|, so g is never below the true excess: if every sample j < res of a piece is inactive (g <= 0), the margin of
+ *     anet_traj_stop_margin_dev with the same pen is >= 0 at those samples.
+ *   - v.v >= 0, so the term dominates the obstacle term of the same clearance, w and smooth_mu: a caller uses one or the other.
+ *   - with a_brake = +inf and t_react = 0 it IS the obstacle term (hb = kappa = 0, G = 0).
+ * gdC, gdT, piece_cost (may be NULL): the shapes of anet_minco_partial_grads_dev.  accumulate = 0: they are written; != 0: the
+ * kernel's complete share is added to the stored value with one unfused addition, bit for bit the sum of the two separate results.
+ * Lanes in [batch, ld) are never touched.  No atomics, no workspace; the outputs of trajectory b have the same bits alone or among
+ * many, and at any ld.  Exact zeros when every sample is inactive, a map of +ANET_DIST_NONE included.  All outputs of b, and only of
+ * b, are NaN when a duration of b is not finite or <= 0, a sample position, velocity or acceleration of b is not finite (v.v or
+ * a.a not finite counts), or d = -inf (the all-blocked map).  Orders 2, 3, 4 (ANET_ERR_UNSUPPORTED otherwise); ANET_ERR_INVALID: a NULL pointer other than
+ * piece_cost, ld < batch, a piece count outside [1, ANET_MAX_PIECES], a bad grid, a penalty outside the ranges below.  batch == 0
+ * returns ANET_OK and touches nothing.                                                                                          */
+typedef struct anet_stop_penalty {
+  double w;          /* weight, >= 0, finite */
+  double smooth_mu;  /* smoothedL1 mu in m, > 0 */
+  double clearance;  /* m, finite: kept on top of the stop distance */
+  double a_brake;    /* m/s^2, > 0; +inf allowed: no braking distance */
+  double t_react;    /* s, >= 0, finite */
+  double speed_eps;  /* m/s, >= 0, finite; > 0 required when t_react > 0 */
+  int32_t res;       /* samples per piece, >= 1 */
+} anet_stop_penalty;
+int anet_minco_stop_partial_grads_dev(anet_ctx *ctx, const anet_stop_penalty *pen, int s, int n_pieces, int64_t batch, int64_t ld,
+                                      const double *coeffs, const double *T, const anet_voxel_grid *grid, const int32_t *sd2,
+                                      int accumulate, double *gdC, double *gdT, double *piece_cost /* may be NULL */, void *stream);
+/* A SAMPLED check, as anet_traj_body_margin (the field is no polynomial in t: nothing bounds the value between the samples): per
+ * piece the minimum over sigma = j / res, tau = sigma T_i, j = 0..res (both ends; the penalty's samples and the piece's end) of
+ *     ((d(p) - clearance) - t_react |v|) - (v.v) hb,          |v| = sqrt(v.v) exactly: no eps
+ * with nothing contracted.  margin >= 0: at every sample the vehicle can stop `clearance` short of the blocked set, by the ball
+ * form (the direction of v is not used).  w, smooth_mu and speed_eps of `pen` are not read (speed_eps must still be >= 0, finite).  margin [N][ld]
+ * (dev) / [batch][N] (host); t (local time), speed (|v|) and dist (d) at the minimiser, the first j on ties: the same shapes, each may
+ * be NULL; they are diagnostics, specified by consistency as those of anet_traj_body_margin are: the expression above at the
+ * piece's p(t), v(t) reproduces margin, and dist - clearance - t_react speed - speed^2 hb does.  A non-finite coefficient or
+ * duration of a piece, or a duration <= 0, gives NaN in all four for that piece only.  A sentinel map gives margin = dist = +-inf.
+ * The host form takes trajectory-major coeffs [batch][N][3][2s] and T [batch][N], staged as anet_traj_voxel_hit stages its own;
+ * sd2 is a DEVICE pointer in both forms: the map lives there.  Errors as above (the optional outputs may be NULL).               */
+int anet_traj_stop_margin_dev(anet_ctx *ctx, const anet_stop_penalty *pen, int s, int n_pieces, int64_t batch, int64_t ld,
+                              const double *coeffs, const double *T, const anet_voxel_grid *grid, const int32_t *sd2, double *margin,
+                              double *t, double *speed, double *dist, void *stream);
+int anet_traj_stop_margin(anet_ctx *ctx, const anet_stop_penalty *pen, int s, int n_pieces, int64_t batch, const double *coeffs,
+                          const double *T, const anet_voxel_grid *grid, const int32_t *sd2 /* DEVICE */, double *margin, double *t,
+                          double *speed, double *dist);
+
 /* ---- whole-body corridor terms: body vertices through the flatness attitude ----------------------------------------------
  * Every other corridor term holds a_r . p(t) <= h_r for the POINT p.  Here the vehicle is a body-fixed convex polytope with vertices
  * b_k, k < K = n_verts <= ANET_MAX_BODY_VERTS, in the body frame in metres, shared by the batch; its attitude is the one the

@@ -20,6 +20,15 @@
 //     double m = getBodyMargin(traj, flatmap, verts, hPolys, 20);  // max of a_r . (p(t) + R(q(t)) b_k) - h_r, piece i against hPolys[i]
 //     if (checkBodyCorridor(traj, flatmap, verts, hPolys, 20)) ...
 // q(t) is the attitude flatmap.forward gives at the trajectory's v, a, j with psi = 0.  A SAMPLED check: res + 1 samples per piece.
+//
+// Stop within known space (anet_traj_stop_margin; no counterpart in the reference): on a map whose blocked set is occupied or
+// unknown (OccupancyMap::toVoxelMap), can the vehicle come to rest inside free space from every sample of the trajectory?
+//     double t; int piece;
+//     double m = getStopMargin(traj, voxelMap, 5.0, 0.1, 0.3, 20, t, piece);  // a_brake 5 m/s^2, t_react 0.1 s, clearance 0.3 m
+//     if (checkStoppable(traj, voxelMap, 5.0, 0.1, 0.3, 20)) ...
+// m is the least  d(p) - clearance - t_react |v| - v.v / (2 a_brake)  over res + 1 samples of every piece, d the map's distance field
+// with walls (VoxelMap::distanceField), t its global time and piece its piece; NaN (t the start of that piece) when a piece has a
+// non-finite coefficient or duration.  A SAMPLED check, and the ball form: the direction of v is not used.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -246,4 +255,48 @@ template <int D, class HPoly>
 inline bool checkBodyCorridor(const Trajectory<D> &traj, const flatness::FlatnessMap &flatmap, const std::vector<anet::Vec3> &verts,
                               const std::vector<HPoly> &hPolys, int res = 20, double tol = 0.0) {
   return getBodyMargin(traj, flatmap, verts, hPolys, res) <= tol;
+}
+
+// The sampled stop margin: the minimum over the pieces, res + 1 samples of each, on map.distanceField(true); t its global time
+template <int D>
+inline double getStopMargin(const Trajectory<D> &traj, const voxel_map::VoxelMap &map, double a_brake, double t_react, double clearance,
+                            int res, double &t, int &piece) {
+  std::vector<double> co, T;
+  anet::detail::pack_pieces<D>(traj, "getStopMargin: empty trajectory", co, T);
+  anet_stop_penalty pen = {};
+  pen.smooth_mu = 1.0;
+  pen.clearance = clearance;
+  pen.a_brake = a_brake;
+  pen.t_react = t_react;
+  pen.res = res;
+  std::vector<double> m(T.size()), tt(T.size());
+  anet::Context &ctx = anet::Context::thread_default();
+  const int32_t *sd2 = map.distanceField(true);  // (flushes the map's buffered fills first)
+  ctx.check(anet_traj_stop_margin(ctx.get(), &pen, (D + 1) / 2, (int)T.size(), 1, co.data(), T.data(), &map.grid(), sd2, m.data(),
+                                  tt.data(), nullptr, nullptr));
+  double best = INFINITY, start = 0.0;
+  t = 0.0;
+  piece = -1;
+  for (size_t i = 0; i < m.size(); ++i) {
+    if (m[i] != m[i]) {  // nothing is known about this piece
+      t = start;
+      piece = (int)i;
+      return m[i];
+    }
+    if (piece < 0 || m[i] < best) {
+      best = m[i];
+      t = start + tt[i];
+      piece = (int)i;
+    }
+    start += T[i];
+  }
+  return best;
+}
+// true when the vehicle can stop `clearance` short of the blocked set from every sample (NaN: false)
+template <int D>
+inline bool checkStoppable(const Trajectory<D> &traj, const voxel_map::VoxelMap &map, double a_brake, double t_react = 0.0,
+                           double clearance = 0.0, int res = 20) {
+  double t;
+  int piece;
+  return getStopMargin(traj, map, a_brake, t_react, clearance, res, t, piece) >= 0.0;
 }
