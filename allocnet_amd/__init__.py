@@ -54,6 +54,10 @@ from .obstacle import (make_obstacle_penalty, minco_obstacle_partial_grads_dev, 
 from . import stop  # noqa: F401
 from .stop import (make_stop_penalty, minco_stop_partial_grads_dev, minco_stop_cost_grad_dev, minco_stop_cost_grad,  # noqa: F401
                    stop_objective_dev, traj_stop_margin, traj_stop_margin_dev, traj_stop_check)
+from . import yaw  # noqa: F401
+from .yaw import (make_yaw_penalty, minco_solve_scalar, minco_solve_scalar_dev, minco_propagate_grad_scalar_dev,  # noqa: F401
+                  minco_yaw_partial_grads_dev, minco_yaw_cost_grad, minco_yaw_cost_grad_dev, yaw_objective_dev, traj_yaw_margin,
+                  traj_yaw_margin_dev, traj_flat_states_yaw, heading_waypoints, YawTrajectory)
 from . import body  # noqa: F401
 from .body import (make_body_penalty, box_body, minco_body_partial_grads_dev, minco_body_cost_grad_dev,  # noqa: F401
                    minco_body_cost_grad, body_objective_dev, traj_body_margin, traj_body_margin_dev)

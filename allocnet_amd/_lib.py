@@ -148,6 +148,17 @@ PROTOTYPES = {
                                                   c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "anet_traj_stop_margin_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64] + [c_void_p] * 9),
     "anet_traj_stop_margin": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64] + [c_void_p] * 8),
+    "anet_minco_solve_scalar_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_int64] + [c_void_p] * 7),
+    "anet_minco_solve_scalar": (c_int, [c_void_p, c_int, c_int, c_int, c_int64] + [c_void_p] * 6),
+    "anet_minco_propagate_grad_scalar_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int64, c_int64] + [c_void_p] * 7),
+    "anet_minco_yaw_partial_grads_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                                 c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "anet_traj_yaw_margin_dev": (c_int, [c_void_p, c_void_p, c_double, c_int, c_int, c_int, c_int64, c_int64] + [c_void_p] * 7),
+    "anet_traj_yaw_margin": (c_int, [c_void_p, c_void_p, c_double, c_int, c_int, c_int, c_int64] + [c_void_p] * 6),
+    "anet_traj_states_yaw_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                              c_int, c_void_p, c_void_p, c_void_p]),
+    "anet_traj_states_yaw": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int,
+                                          c_void_p, c_void_p]),
     "anet_voxel_path_workspace": (c_int64, [c_void_p, c_int64]),
     "anet_voxel_path_field_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                           c_void_p]),
@@ -304,6 +315,12 @@ class StopPenalty(ctypes.Structure):
     """struct anet_stop_penalty (include/allocnet_amd.h)."""
     _fields_ = [("w", c_double), ("smooth_mu", c_double), ("clearance", c_double), ("a_brake", c_double), ("t_react", c_double),
                 ("speed_eps", c_double), ("res", ctypes.c_int32)]
+
+
+class YawPenalty(ctypes.Structure):
+    """struct anet_yaw_penalty (include/allocnet_amd.h)."""
+    _fields_ = [("w_look", c_double), ("mu_look", c_double), ("half_fov", c_double), ("speed_eps", c_double), ("w_rate", c_double),
+                ("mu_rate", c_double), ("max_rate", c_double), ("w_energy", c_double), ("res", ctypes.c_int32)]
 
 
 ANET_MAX_BODY_VERTS = 16

@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(LIB_DIR, "liballocnet_amd.so")
 SOURCES = ["api_context.hip", "api_solve.hip", "api_cost_grad.hip", "api_lbfgs.hip", "api_qp.hip", "api_voxel.hip",
            "api_flatness.hip", "api_timenet.hip", "api_polytope.hip", "api_sfc.hip", "api_margin.hip",
            "api_voxel_hit.hip", "api_clearance.hip", "api_separation.hip", "api_avoid.hip", "api_distance.hip", "api_body.hip",
-           "api_occupancy.hip", "api_stop.hip"]
+           "api_occupancy.hip", "api_stop.hip", "api_yaw.hip"]
 # translation units with flags of their own: (source, extra flags)
 UNITS = [("piece_grad_unit.hip", ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
          ("qp_ipm_fuse_unit.hip", ["-mllvm", "-amdgpu-sched-strategy=max-ilp"])]

@@ -22,6 +22,7 @@
 //   api_avoid.hip      trajectory-avoidance penalty of the MINCO objective against neighbours of another set of trajectories
 //   api_distance.hip   exact distance field of the voxel map, its query, the obstacle penalty of the MINCO objective
 //   api_stop.hip       stop within known space: the penalty that couples speed with the distance field, and its sampled margin
+//   api_yaw.hip        yaw trajectories: one-axis MINCO, the field-of-view / yaw-rate penalty, its sampled margin, flat states with yaw
 //   api_body.hip       whole-body corridor terms: body vertices through the flatness attitude, penalty gradients and sampled margin
 //   api_occupancy.hip  log-odds occupancy grid from sensor scans (ray carving), depth unprojection, first hit of a segment on the byte grid;
 //                      exploration goals on it (frontier_kernels.h, which builds on occupancy_kernels.h): frontier, components, view gain

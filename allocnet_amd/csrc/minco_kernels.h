@@ -660,7 +660,9 @@ struct PropArgs {
 // the previous step of the sweep it is used in.  Without the masks of the generic code the body is one straight-line
 // block and the scheduler computes every piece's powers of 1/T up front for all three sweeps, which spills
 // (~1 KB/lane); the false dependency keeps each piece's powers next to their use.
-template <int S, int NB, bool CHAIN = false, bool PIPE = CHAIN>
+// NAX: the axes interleaved in coeffs, gdC (rows (piece * NAX + ax) * D + col) and gradP (rows (k - 1) * NAX + ax): 3 for a
+// position trajectory, 1 for the one-axis MINCO of yaw_kernels.h.
+template <int S, int NB, bool CHAIN = false, bool PIPE = CHAIN, int NAX = 3>
 __device__ __forceinline__ void propagate_axis(const Factor<S, NB> &F, const int N, const int np, const PropArgs &a,
                                                const int64_t b, const int ax, const double Tlast,
                                                double (&gT)[NB], const bool store) {
@@ -682,7 +684,7 @@ __device__ __forceinline__ void propagate_axis(const Factor<S, NB> &F, const int
 #pragma unroll
       for (int j = 0; j < S; ++j) {
         if (j > 0) fact *= (double)j;
-        x[j] = fact * cb[(int64_t)(k * 3 * D + (D - 1 - j)) * ld];
+        x[j] = fact * cb[(int64_t)(k * NAX * D + (D - 1 - j)) * ld];
       }
     } else {
       double cl[D], tp[D];
@@ -690,7 +692,7 @@ __device__ __forceinline__ void propagate_axis(const Factor<S, NB> &F, const int
 #pragma unroll
       for (int e = 1; e < D; ++e) tp[e] = tp[e - 1] * Tlast;
 #pragma unroll
-      for (int col = 0; col < D; ++col) cl[col] = cb[(int64_t)((N - 1) * 3 * D + col) * ld];
+      for (int col = 0; col < D; ++col) cl[col] = cb[(int64_t)((N - 1) * NAX * D + col) * ld];
 #pragma unroll
       for (int j = 0; j < S; ++j) {
         double acc = 0.0;
@@ -742,7 +744,7 @@ __device__ __forceinline__ void propagate_axis(const Factor<S, NB> &F, const int
         }
         if (i + 1 < N) {
 #pragma unroll
-          for (int col = 0; col < D; ++col) gnext[col] = ga[(int64_t)((i + 1) * 3 * D + col) * ld];
+          for (int col = 0; col < D; ++col) gnext[col] = ga[(int64_t)((i + 1) * NAX * D + col) * ld];
         }
         if (i + 2 < N) node_state(ca, i + 2, xn2);
 #pragma unroll
@@ -752,7 +754,7 @@ __device__ __forceinline__ void propagate_axis(const Factor<S, NB> &F, const int
         }
       } else {
 #pragma unroll
-        for (int col = 0; col < D; ++col) gc[col] = ga[(int64_t)(i * 3 * D + col) * ld];
+        for (int col = 0; col < D; ++col) gc[col] = ga[(int64_t)(i * NAX * D + col) * ld];
         node_state(ca, i, x0);
         node_state(ca, i + 1, x1);
       }
@@ -850,7 +852,7 @@ __device__ __forceinline__ void propagate_axis(const Factor<S, NB> &F, const int
   });
 #pragma unroll
   for (int k = 1; k < NB; ++k)
-    if (k < N && store) gp[(int64_t)((k - 1) * 3) * ld] = GP[k];
+    if (k < N && store) gp[(int64_t)((k - 1) * NAX) * ld] = GP[k];
 }
 
 // MINCO propogateGrad: given the partial gradients (gdC, gdT) of a scalar J(c, T), return its total

@@ -726,6 +726,30 @@ class Trajectory:
         """True when the sampled stop margin is >= 0 on every piece; a NaN margin is False."""
         return bool(self.getStopMargin(vm, a_brake, t_react, clearance, res)[0] >= 0.0)
 
+    # --- yaw: the direction of travel inside the field of view, the yaw rate under its limit (yaw.py) -------------------
+    def getYawMargin(self, yaw, half_fov, v_min=0.0, res=20, per_piece=False):
+        """(margin, t, piece): the least half_fov - |angle between the horizontal velocity and the heading| over the res + 1
+        samples of every piece with |v_xy| >= v_min, the global time at which it is attained and its piece; yaw is a YawTrajectory
+        over the same durations.  +inf when no sample moves that fast.  A sampled check.  per_piece=True: the arrays (margin, t,
+        rate) over the pieces, t in local time, rate the largest sampled |dpsi|."""
+        from .yaw import traj_yaw_margin
+        co, T = self._arrays()
+        if yaw.getPieceNum() != len(self.pieces) or not np.array_equal(yaw.getDurations(), T[0]):
+            raise ValueError("the yaw trajectory must share the pieces and durations")
+        m, t, r = traj_yaw_margin(co, yaw.coeffs[None], T, half_fov, v_min, res, ctx=self._ctx)
+        if per_piece:
+            return m[0], t[0], r[0]
+        if np.isnan(m[0]).any():
+            i = int(np.isnan(m[0]).argmax())
+            return float("nan"), float(T[0, :i].sum()), i
+        i = int(m[0].argmin())
+        return float(m[0, i]), float(T[0, :i].sum() + t[0, i]), i
+
+    def checkYaw(self, yaw, half_fov, max_rate, v_min=0.0, res=20):
+        """True when the sampled look margin is >= 0 on every piece and the sampled |dpsi| stays within max_rate; NaN is False."""
+        m, _, r = self.getYawMargin(yaw, half_fov, v_min, res, per_piece=True)
+        return bool((m >= 0.0).all() and (r <= max_rate).all())
+
     # --- junctions (trajectory.hpp:540-574): direct coefficient reads except at the very end
     def getPositions(self):
         N = self.getPieceNum()

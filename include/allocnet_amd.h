@@ -1090,6 +1090,87 @@ int anet_traj_stop_margin(anet_ctx *ctx, const anet_stop_penalty *pen, int s, in
                           const double *T, const anet_voxel_grid *grid, const int32_t *sd2 /* DEVICE */, double *margin, double *t,
                           double *speed, double *dist);
 
+/* ---- yaw trajectories: one-axis MINCO, field of view and yaw rate (no counterpart in the reference) ---------------------------
+ * A quadrotor has four flat outputs; the heading psi is the fourth.  It is carried as a second, ONE-AXIS minimum-control polynomial
+ * over the SAME pieces and durations as the position trajectory, with an order sy in {2, 3, 4} of its own.  psi is an unwrapped real
+ * number in radians: nothing wraps it.  Yaw coefficients are [N * 2 sy][ld] (dev) / [batch][N][2 sy] (host), highest power first.
+ *
+ * anet_minco_solve_scalar[_dev]: anet_minco_solve[_dev] for one axis.  head, tail [c][ld], wps [N - 1][ld] (ignored at N = 1),
+ * T [N][ld]; coeffs [N * 2s][ld] or NULL, energy [ld] or NULL (int (psi^(s))^2 dt).  Host: head, tail [batch][c]; wps [batch][N - 1];
+ * T [batch][N]; coeffs [batch][N][2s]; energy [batch].  The arithmetic is that of one axis of anet_minco_solve_dev's lane-per-
+ * trajectory kernel at ANET_MAX_PIECES pieces (no wide-spread redo in the host form).
+ * anet_minco_propagate_grad_scalar_dev: anet_minco_propagate_grad_dev for one axis: gdC [N * 2s][ld], gradP [max(N - 1, 1)][ld],
+ * gradT [N][ld].  gdT [N][ld] may be NULL (= zeros): the durations are shared with the position trajectory, so a joint objective
+ * adds the direct dJ/dT once, on the position side, and takes only the adjoint's share from here.
+ * Errors of both: those of anet_minco_solve_dev / anet_minco_propagate_grad_dev.                                                 */
+int anet_minco_solve_scalar_dev(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batch, int64_t ld, const double *head,
+                                const double *tail, const double *wps, const double *T, double *coeffs /* may be NULL */,
+                                double *energy /* may be NULL */, void *stream);
+int anet_minco_solve_scalar(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batch, const double *head, const double *tail,
+                            const double *wps, const double *T, double *coeffs, double *energy);
+int anet_minco_propagate_grad_scalar_dev(anet_ctx *ctx, int s, int c, int n_pieces, int64_t batch, int64_t ld, const double *T,
+                                         const double *coeffs, const double *gdC, const double *gdT /* may be NULL */, double *gradP,
+                                         double *gradT, void *stream);
+/* The yaw penalty.  Sampling, layouts, the sum and the accumulate contract are those of anet_minco_stop_partial_grads_dev: sample
+ * j < res of piece i at sigma = (double)j / (double)res, tau = sigma * T_i, one rounding each.  h = (v_x, v_y) and (a_x, a_y) of the
+ * position piece and psi, dpsi, ddpsi of the yaw piece at tau, by one Horner recurrence each; (sin psi, cos psi) from one sincos;
+ * ca = cos(half_fov), computed once on the host:
+ *     s_eps  = sqrt(h.h + eps^2)                                    (eps = speed_eps)
+ *     g_look = ca s_eps - (h_x cos psi + h_y sin psi)   [m/s]       Phi_look = w_look smoothedL1_mu_look(g_look)
+ *     g_rate = dpsi^2 - max_rate^2                      [(rad/s)^2] Phi_rate = w_rate smoothedL1_mu_rate(g_rate)
+ *     G = w_look phi'_look (ca h / s_eps - (cos psi, sin psi))      (x and y only; the z rows receive nothing)
+ *     A = w_look phi'_look (h_x sin psi - h_y cos psi)              R = w_rate phi'_rate 2 dpsi
+ *     J_yaw(b)           = sum_i (T_i / res) sum_(j < res) (Phi_look + Phi_rate)  +  w_energy sum_i int_0^T_i (psi^(sy))^2 dt
+ *     dJ/dc [i][ax][k]   = (T_i / res) sum_j G_ax k tau^(k-1)                              ax in {x, y}
+ *     dJ/dcy[i][k]       = (T_i / res) sum_j (A tau^k + R k tau^(k-1))  +  the effort term's closed form
+ *     dJ/dT_i            = (1/res) sum_j (Phi_look + Phi_rate) + (T_i/res) sum_j sigma (G . a_xy + A dpsi + R ddpsi)
+ *                          + w_energy (psi^(sy)(T_i))^2
+ * Two properties: s_eps >= |h| and ca >= 0, so g_look is never below the true excess ca |h| - h.u: a sample that is inactive in
+ * the look term has its horizontal velocity inside the field of view (which is why half_fov > pi/2 is ANET_ERR_INVALID); and the
+ * look term scales with speed: at rest any heading is free, up to the ca eps the smoothing leaves.
+ * gdC [N*3*2s][ld], gdT [N][ld], piece_cost [N][ld] (may be NULL; the effort of a piece included) are shared with the position
+ * terms: accumulate = 0 writes them (all of gdC, zeros in the z rows); != 0 adds the kernel's complete share to the stored value
+ * with one unfused addition.  gdCy [N*2sy][ld] is always overwritten.  A weight of 0 skips its term (its mu, and speed_eps for
+ * w_look, are then not read); all three 0 give exact zeros.  Lanes in [batch, ld) are never touched.  No atomics, no workspace; the
+ * outputs of trajectory b have the same bits alone or among many, and at any ld.  All outputs of b, and only of b, are NaN when a
+ * duration of b is not finite or <= 0, a position or yaw coefficient of b is not finite, or a sample value is not finite.
+ * Orders s, sy outside 2..4: ANET_ERR_UNSUPPORTED.  ANET_ERR_INVALID: a NULL pointer other than piece_cost, ld < batch, a piece
+ * count outside [1, ANET_MAX_PIECES], a penalty outside the ranges below.  batch == 0 returns ANET_OK and touches nothing.         */
+typedef struct anet_yaw_penalty {
+  double w_look, mu_look;    /* weight, >= 0, finite; smoothedL1 mu in m/s, > 0 when w_look > 0                 */
+  double half_fov;           /* horizontal half field of view alpha in rad, 0 < alpha <= pi/2                  */
+  double speed_eps;          /* smoothing of |v_xy| in m/s, > 0 when w_look > 0                                */
+  double w_rate, mu_rate;    /* weight; mu in (rad/s)^2, > 0 when w_rate > 0                                   */
+  double max_rate;           /* rad/s, > 0, +inf allowed                                                       */
+  double w_energy;           /* weight of int (psi^(sy))^2 dt, >= 0; 0: the term is skipped                    */
+  int32_t res;               /* samples per piece, >= 1                                                        */
+} anet_yaw_penalty;
+int anet_minco_yaw_partial_grads_dev(anet_ctx *ctx, const anet_yaw_penalty *pen, int s, int sy, int n_pieces, int64_t batch, int64_t ld,
+                                     const double *coeffs, const double *ycoeffs, const double *T, int accumulate, double *gdC,
+                                     double *gdCy, double *gdT, double *piece_cost /* may be NULL */, void *stream);
+/* A SAMPLED check, as anet_traj_stop_margin (nothing bounds the angle between the samples): per piece, over sigma = j / res,
+ * tau = sigma T_i, j = 0..res (the penalty's samples and the piece's end), among the samples with |h| >= v_min (m/s, >= 0, finite),
+ *     margin = half_fov - |atan2(h x u, h . u)|,   u = (cos psi, sin psi),  h x u = h_x sin psi - h_y cos psi,  |h| exact, no eps
+ * with nothing contracted: the first minimum over j, and its local time in t.  A piece with no such sample reports +inf and time
+ * 0.  A sample at rest (|h| = 0, which counts only at v_min = 0) has no direction: its angle is 0.  rate: the largest |dpsi| over all
+ * res + 1 samples.  margin, t, rate [N][ld] (dev) / [batch][N] (host); t and rate may be
+ * NULL.  Only half_fov and res of `pen` are read.  A non-finite coefficient (position or yaw) or duration of a piece, or a
+ * duration <= 0, gives NaN in all three for that piece only.  The host form takes trajectory-major coeffs [batch][N][3][2s],
+ * ycoeffs [batch][N][2sy] and T [batch][N].  Errors as above.                                                                    */
+int anet_traj_yaw_margin_dev(anet_ctx *ctx, const anet_yaw_penalty *pen, double v_min, int s, int sy, int n_pieces, int64_t batch,
+                             int64_t ld, const double *coeffs, const double *ycoeffs, const double *T, double *margin, double *t,
+                             double *rate, void *stream);
+int anet_traj_yaw_margin(anet_ctx *ctx, const anet_yaw_penalty *pen, double v_min, int s, int sy, int n_pieces, int64_t batch,
+                         const double *coeffs, const double *ycoeffs, const double *T, double *margin, double *t, double *rate);
+/* anet_traj_flat_states[_dev] with the yaw: the same piece location and the same 11 fields per query, with psi, dpsi evaluated from
+ * the yaw piece at the same local time and the flatness map taken with them (anet_flat_forward with psi, dpsi given).  A zero yaw
+ * polynomial reproduces anet_traj_flat_states.                                                                                  */
+int anet_traj_states_yaw_dev(anet_ctx *ctx, const anet_flat_params *params, int s, int sy, int n_pieces, int64_t batch, int64_t ld,
+                                  const double *coeffs, const double *ycoeffs, const double *T, int nq, const double *tq, double *out,
+                                  void *stream);
+int anet_traj_states_yaw(anet_ctx *ctx, const anet_flat_params *params, int s, int sy, int n_pieces, int64_t batch,
+                              const double *coeffs, const double *ycoeffs, const double *T, int nq, const double *tq, double *out);
+
 /* ---- whole-body corridor terms: body vertices through the flatness attitude ----------------------------------------------
  * Every other corridor term holds a_r . p(t) <= h_r for the POINT p.  Here the vehicle is a body-fixed convex polytope with vertices
  * b_k, k < K = n_verts <= ANET_MAX_BODY_VERTS, in the body frame in metres, shared by the batch; its attitude is the one the
